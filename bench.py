@@ -10,11 +10,26 @@ seeded xavier weights (tests/golden/weights_seed0.npz = torch.manual_seed(0)
 BackgammonPolicyNetwork()), T = 1.5 (ParameterManager version 1).
 
 Workload: 8,192 game lanes per GPU (weak scaling; N = 8 is configs[3]/[4]'s
-65,536 lanes sharded across 8 MI355X), 1-ply softmax select as the headline,
-with 2-ply K=4 (configs[4]) and K=all (configs[2]'s ~21 x C reply boards per
-decision) legs on the same lanes, and at N = 1 configs[1] (4,096 lanes) beside.
+65,536 lanes sharded across 8 MI355X), 1-ply softmax select as the headline.
 
-N = 1:  python bench.py
+A plain run (python bench.py --gpus 1 --steps N --warmup W) does only what
+the headline needs: it creates the engine, spreads the lanes over their games
+(--desync-steps), warms up, times the N steps and prints the JSON line.
+--full adds everything else, as fields of the same line: the CPU baseline
+(before the GPU is touched), the event-timed pass behind `roofline` /
+`kernels`, the 2-ply K=4 (configs[4]) and K=all (configs[2]'s ~21 x C reply
+boards per decision) legs on the same lanes, at N = 1 configs[1] / configs[2]
+(4,096 lanes) beside, and without --steps SURVEY 8d's protocol (seeds 0-4, a
+timed window of >= --window-s seconds each, the median reported).
+
+--dump-outputs DIR writes what the headline leg's last timed harvest handed
+to its caller (rank 0's lanes), decoded to float32 .npy files (dump_outputs
+below). That leg is then made reproducible: lockstep launches instead of the
+balanced ones (which let each lane get a different distance per launch, so the
+set of episodes in a harvest differs from run to run) and no --desync-ms time
+floor; the line's config.engine says so. Same arguments, same files.
+
+N = 1:  python bench.py [--full]
 N > 1:  python bench.py --gpus N      (starts N rank processes itself through
             torch.distributed.run before anything touches a GPU), or as the
             driver does: python -m torch.distributed.run --nnodes=1
@@ -115,15 +130,70 @@ def sum_over_ranks(x, world):
     return float(t.item())
 
 
+DUMP_LANES = 256          # --dump-outputs: a fixed seeded sample of a rank's lanes
+DUMP_MAX_BYTES = 60 << 20  # ... and at most this much in all (whole episodes, in (lane, episode no.) order)
+BOARD_COLS = 53           # positions_0[24] | positions_1[24] | bar[2] | borne_off[2] | indicator player
+
+
+def _unpack_boards(p):
+    """Packed boards uint32 [n, >= 7] (include/bgx.h) -> float32 [n, 53]."""
+    sh = (4 * np.arange(8, dtype=np.uint32))[None, None, :]
+    pts = ((p[:, :6, None] >> sh) & 15).reshape(len(p), 48)
+    w6 = p[:, 6]
+    tail = np.stack([w6 & 15, (w6 >> 4) & 15, (w6 >> 8) & 15, (w6 >> 12) & 15, (w6 >> 16) & 1], 1)
+    return np.concatenate([pts, tail], 1).astype(np.float32)
+
+
+def dump_outputs(path, headers, records, lane_base, lanes, counters):
+    """--dump-outputs: the last timed harvest (Engine.harvest_fetch's headers
+    [n, 16] and records [m, 12], host copies) of a seeded sample of DUMP_LANES
+    lanes, in (lane, episode no.) order, decoded field by field to float32:
+      episodes.npy [n', 60]: global lane, episode no., n_records, env steps, win_type, winner, flags,
+                             the final board (53: the u8[52] board, then the indicator player)
+      records.npy  [m', 68]: global lane, episode no., the board before the move (53), V(s), V(a), reward,
+                             action, n_moves, step, dice0, dice1, done, close_out, prime, mover, win_type
+      stats.npy    [5] float64: the timed window's env_steps, decisions, episodes, value_rows, movegen_jobs
+    Every integer field is exact in float32 (< 2^24)."""
+    from bgx.records import EP_WORDS, REC_WORDS, episode_bounds, fields
+    h = np.ascontiguousarray(headers).view(np.uint32).reshape(-1, EP_WORDS)
+    r = np.ascontiguousarray(records).view(np.uint32).reshape(-1, REC_WORDS)
+    sample = lane_base + np.sort(np.random.default_rng(20240).permutation(lanes)[:DUMP_LANES])
+    first = episode_bounds(h)[0][:-1]   # each episode's records are contiguous, in header order
+    keep = np.flatnonzero(np.isin(h[:, 0], sample))
+    keep = keep[np.lexsort((h[keep, 1], h[keep, 0]))]
+    row_bytes = 4 * (7 + BOARD_COLS) + 4 * (15 + BOARD_COLS) * h[keep, 3].astype(np.int64)
+    keep = keep[np.cumsum(row_bytes) <= DUMP_MAX_BYTES]
+    h, first = h[keep], first[keep]
+    n = h[:, 3].astype(np.int64)
+    ep_of = np.repeat(np.arange(len(h)), n)                       # the episode of every kept record
+    idx = first[ep_of] + np.arange(n.sum()) - np.repeat(np.cumsum(n) - n, n)
+    r = r[idx]
+    w5 = h[:, 5]
+    eps = np.concatenate([np.stack([h[:, 0], h[:, 1], h[:, 3], h[:, 4], w5 & 255, (w5 >> 8) & 255, w5 >> 16],
+                                   1).astype(np.float32), _unpack_boards(h[:, 6:13])], 1)
+    f = fields(r)
+    recs = np.concatenate([h[ep_of, :2].astype(np.float32), _unpack_boards(r[:, :7]),
+                           np.stack([f["v_s"], f["v_a"], f["reward"]], 1),
+                           np.stack([f["action"], f["n_moves"], f["step"], f["dice"][:, 0], f["dice"][:, 1],
+                                     f["done"], f["close_out"], f["prime"], f["mover"], f["win_type"]],
+                                    1).astype(np.float32)], 1)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "episodes.npy"), eps)
+    np.save(os.path.join(path, "records.npy"), recs)
+    np.save(os.path.join(path, "stats.npy"), np.array(
+        [counters[k] for k in ("env_steps", "decisions", "episodes", "value_rows", "movegen_jobs")], np.float64))
+
+
 def run_engine(args, world, rank, ply, k_top, lanes, steps, warmup, harvest_every, timing, timing_steps=0,
-               desync=0, seed=None):
+               desync=0, seed=None, dump=False):
     from bgx import Engine
     from bgx import dist as bdist
     w = load_weights()
     if world > 1:
         w = bdist.broadcast_weights(w)
+    reproducible = dump   # the --dump-outputs leg, on every rank: lockstep launches, no time floor under the desync
     eng = Engine(lanes=lanes, seed=args.seed if seed is None else seed, ply=ply, k_top=k_top, lane_base=rank * lanes,
-                 fused=not args.no_fused, balance=not args.no_balance)
+                 fused=not args.no_fused, balance=not args.no_balance and not reproducible)
     eng.set_weights(w, temperature=1.5, version=1)
     gathered = [0, 0]
     harvested = [0, 0]   # this rank's own harvests (episodes, records), every run() of the engine
@@ -139,6 +209,7 @@ def run_engine(args, world, rank, ply, k_top, lanes, steps, warmup, harvest_ever
         hg = mod.setup(rank, world, hostgather.slot_bytes_for(lanes, args.harvest_every), dst=0,
                        device=torch.cuda.current_device())
     seq = [0]
+    last_ticket = [None]
 
     def run(n):
         # The harvest is queued behind each launch (harvest_enqueue) and the next
@@ -200,7 +271,7 @@ def run_engine(args, world, rank, ply, k_top, lanes, steps, warmup, harvest_ever
             t = eng.harvest_enqueue()
             if pending_t is not None:
                 consume(pending_t)
-            pending_t = t
+            pending_t = last_ticket[0] = t
             left -= k
         if pending_t is not None:
             consume(pending_t)
@@ -219,7 +290,7 @@ def run_engine(args, world, rank, ply, k_top, lanes, steps, warmup, harvest_ever
     desync_run = desync
     while True:   # the same number of extra chunks on every rank (the gathers count batches)
         eng.sync()
-        more = (time.perf_counter() - t_ds) * 1e3 < args.desync_ms
+        more = not reproducible and (time.perf_counter() - t_ds) * 1e3 < args.desync_ms
         if world > 1:
             more = max_over_ranks(1.0 if more else 0.0, world) > 0
         if not more:
@@ -238,6 +309,11 @@ def run_engine(args, world, rank, ply, k_top, lanes, steps, warmup, harvest_ever
     s1 = eng.stats()
     d = {k: s1[k] - s0[k] for k in s1}
     d["collect_s"], d["collect_batches"] = collect_t[0] - c0[0], collect_t[1] - c0[1]   # the timed window's
+    if dump and rank == 0:
+        # the last timed harvest again, this time read: fetching a ticket twice is
+        # allowed, and its arrays stay valid until the second enqueue after it
+        h = eng.harvest_fetch(last_ticket[0])
+        d["dump"] = (h.headers.cpu().numpy(), h.records.cpu().numpy())
     tm = d_tm = None
     if timing:
         # per-kernel durations: a second pass of the same workload with HIP
@@ -464,9 +540,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None,
-                    help="timed steps of the headline leg (the driver passes it: one run at --seed). Without it, "
-                         "SURVEY 8d's protocol: every leg over seeds 0-4, each with a timed window of >= "
-                         "--window-s seconds, the median reported")
+                    help="timed steps of the headline leg (one run at --seed; 1200 when not given). With --full and "
+                         "without --steps, SURVEY 8d's protocol: every leg over seeds 0-4, each with a timed "
+                         "window of >= --window-s seconds, the median reported")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline leg: the CPU baseline, the event-timed pass behind roofline / kernels, "
+                         "the 2-ply and 4,096-lane legs, and without --steps the protocol")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline leg's last timed harvest as DIR/episodes.npy, records.npy, stats.npy "
+                         "(float32 / float64; a seeded sample of lanes); the run is then lockstep and its desync "
+                         "has no time floor, so that the same arguments give the same files")
     ap.add_argument("--warmup", type=int, default=300)
     ap.add_argument("--window-s", type=float, default=10.0, help="protocol mode: timed seconds per leg and seed")
     ap.add_argument("--seeds", type=int, default=5, help="protocol mode: seeds 0..n-1")
@@ -515,9 +598,16 @@ def main():
         sys.exit(spawn_ranks(args.gpus))
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
 
-    # the CPU baseline first, on rank 0 at N = 1, before this process touches the GPU
+    if args.steps is None and not args.full:
+        args.steps = 1200
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and args.steps is None:
+        ap.error("--dump-outputs needs --steps (one run at --seed, not the protocol's several)")
+
+    # --full: the CPU baseline first, on rank 0 at N = 1, before this process touches the GPU
     cpu = None
-    if world_env == 1 and not args.no_cpu_baseline:
+    if args.full and world_env == 1 and not args.no_cpu_baseline:
         r = cpu_baseline(args.cpu_procs, args.cpu_seconds, list(range(args.cpu_seeds)), args.cpu_2ply_seconds)
         cpu = {"value": r["1ply"]["median"], "unit": "env_steps/s", "cores": r["cores_used"], "kind": "port",
                "sample": (f"{args.cpu_procs} processes, each pinned to one host core, x {args.cpu_seconds:.0f} s "
@@ -538,11 +628,11 @@ def main():
 
     world, rank, local = init_dist()
 
-    def leg(ply, k_top, lanes, steps, warmup, timing_steps, name, desync=None, seed=None):
+    def leg(ply, k_top, lanes, steps, warmup, timing_steps, name, desync=None, seed=None, dump=False):
         desync = args.desync_steps if desync is None else desync
         el_, d_, tm_, dtm_, gathered_, harvested_ = run_engine(args, world, rank, ply, k_top, lanes, steps, warmup,
                                                    args.harvest_every, timing=timing_steps > 0,
-                                                   timing_steps=timing_steps, desync=desync, seed=seed)
+                                                   timing_steps=timing_steps, desync=desync, seed=seed, dump=dump)
         el_ = max_over_ranks(el_, world)
         per_rank = [int(x) for x in all_ranks(d_["env_steps"], world)]
         roof_, kern_ = roofline_for(dtm_, tm_, name, lanes) if timing_steps > 0 else (None, None)
@@ -592,33 +682,37 @@ def main():
                            "median_seed": med["seed"], "calibration_steps": short_steps}
         return med, dmed
 
-    proto = args.steps is None
+    proto = args.steps is None   # --full without --steps
     head_name = "1ply" if args.ply == 1 else ("2ply_k4" if args.k_top == 4 else "2ply_kall")
     if proto:
         head, d = protocol(args.ply, args.k_top, args.lanes, args.warmup, args.timing_steps, head_name, 1200)
         args.steps = head["steps"]
     else:
-        head, d = leg(args.ply, args.k_top, args.lanes, args.steps, args.warmup, min(args.steps, args.timing_steps),
-                      head_name)
+        head, d = leg(args.ply, args.k_top, args.lanes, args.steps, args.warmup,
+                      min(args.steps, args.timing_steps) if args.full else 0, head_name,
+                      dump=args.dump_outputs is not None)
+        if "dump" in d:
+            dump_outputs(args.dump_outputs, *d["dump"], rank * args.lanes, args.lanes, d)
     extra = {}
-    if args.ply == 1 and args.two_ply_steps > 0:
+    side = args.full and args.ply == 1   # the legs beside the headline
+    if side and args.two_ply_steps > 0:
         extra["two_ply_k4"], _ = (protocol(2, 4, args.lanes, 20, min(args.timing_steps, 50), "2ply_k4", 100)
                                   if proto else
                                   leg(2, 4, args.lanes, args.two_ply_steps, 20,
                                       min(args.two_ply_steps, args.timing_steps, 50), "2ply_k4"))
-    if args.ply == 1 and args.kall_steps > 0:
+    if side and args.kall_steps > 0:
         extra["two_ply_kall"], d3 = (protocol(2, 0, args.lanes, 5, min(args.timing_steps, 10), "2ply_kall", 20)
                                      if proto else
                                      leg(2, 0, args.lanes, args.kall_steps, 5,
                                          min(args.kall_steps, args.timing_steps, 10), "2ply_kall"))
         extra["two_ply_kall"]["reply_boards_per_decision"] = \
             (d3["value_rows"] - d3["gap_rows"] - 2 * d3["env_steps"]) / max(1, d3["decisions"])
-    if args.ply == 1 and world == 1 and args.config1_steps > 0 and args.lanes != 4096:
+    if side and world == 1 and args.config1_steps > 0 and args.lanes != 4096:
         c1, _ = (protocol(1, 4, 4096, 100, min(args.config1_steps, args.timing_steps), "1ply", 600) if proto else
                  leg(1, 4, 4096, args.config1_steps, 100, min(args.config1_steps, args.timing_steps), "1ply"))
         extra["configs1_4096_lanes"] = {k: c1[k] for k in ("value", "unit", "steps", "ms_per_step", "roofline")
                                         + (("protocol",) if proto else ())}
-    if args.ply == 1 and world == 1 and args.config2_steps > 0 and args.lanes != 4096:
+    if side and world == 1 and args.config2_steps > 0 and args.lanes != 4096:
         # configs[2]: 4,096 lanes, 2-ply on one MI355X (its "~21^2 next-boards/step" is K=all; K=4 is the
         # reference's two_ply.py:67-70 default), both legs at that lane count
         keys = ("value", "unit", "steps", "ms_per_step", "decisions_per_s", "gap_rows_frac", "roofline", "kernels")
@@ -643,7 +737,9 @@ def main():
                                        if args.lanes == 8192 else "")),
                        "lanes_per_gpu": args.lanes, "lanes_total": args.lanes * world, "ply": args.ply,
                        "harvest_every": args.harvest_every,
-                       "engine": ("fused step kernel" + ("" if args.no_balance else ", balanced launches")
+                       "engine": ("fused step kernel" + (", lockstep launches (reproducible: --dump-outputs)"
+                                                         if args.dump_outputs is not None else
+                                                         "" if args.no_balance else ", balanced launches")
                                   if args.ply == 1 and not args.no_fused else "phased launches"),
                        "parallelism": ((f"lanes sharded x{world}, episode gather to rank 0 over the DMA engines "
                                         f"into page-locked host memory (memfd segments)" if args.gather == "host"

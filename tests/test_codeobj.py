@@ -34,7 +34,10 @@ def _code_objects(tmp_path):
     if shutil.which("objcopy") is None or not os.path.exists(LIB):
         pytest.skip("objcopy or libbgx.so missing")
     fat = tmp_path / "fatbin.bin"
-    subprocess.run(["objcopy", "--dump-section", f".hip_fatbin={fat}", LIB], check=True, capture_output=True)
+    # with an output file of its own: without one objcopy rewrites libbgx.so in place, under the
+    # feet of a process that has it mapped (the suite's own, once another test has loaded it)
+    subprocess.run(["objcopy", "--dump-section", f".hip_fatbin={fat}", LIB, str(tmp_path / "libbgx.copy.so")],
+                   check=True, capture_output=True)
     data = fat.read_bytes()
     starts = [m.start() for m in re.finditer(re.escape(b"__CLANG_OFFLOAD_BUNDLE__"), data)]
     assert starts, "no offload bundle in libbgx.so"

@@ -16,10 +16,10 @@ if [ $LANES = 8192 ]; then
   P=""; LA=""
   rm -rf $OUT; mkdir -p $OUT
   echo "[1/4] bench (the driver command: --steps 20 --warmup 5)"
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
   tail -c 300 $OUT/bench.json
   echo "[2/4] kernel trace + stats of the bench command"
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/ktrace -o run --output-format csv -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/ktrace.err || { tail $OUT/ktrace.err; exit 1; }
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/ktrace -o run --output-format csv -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/ktrace.err || { tail $OUT/ktrace.err; exit 1; }
 else
   P="l${LANES}_"; LA="--lanes $LANES"
   mkdir -p $OUT
@@ -27,11 +27,11 @@ fi
 echo "[3/4] PMC traffic passes ($LANES lanes)"
 for leg in 1ply_fused 2ply_k4 2ply_kall; do
   if [ $leg = 1ply_fused ]; then
-    ARGS="--steps 600 --warmup 300 --timing-steps 300 --two-ply-steps 0 --kall-steps 0 --config1-steps 0 --config2-steps 0 --no-cpu-baseline"; RX="fused_step"
+    ARGS="--full --steps 600 --warmup 300 --timing-steps 300 --two-ply-steps 0 --kall-steps 0 --config1-steps 0 --config2-steps 0 --no-cpu-baseline"; RX="fused_step"
   elif [ $leg = 2ply_k4 ]; then
-    ARGS="--ply 2 --steps 60 --warmup 20 --timing-steps 1 --two-ply-steps 0 --kall-steps 0 --config1-steps 0 --config2-steps 0 --no-cpu-baseline"; RX="movegen|mlp_kernel"
+    ARGS="--full --ply 2 --steps 60 --warmup 20 --timing-steps 1 --two-ply-steps 0 --kall-steps 0 --config1-steps 0 --config2-steps 0 --no-cpu-baseline"; RX="movegen|mlp_kernel"
   else
-    ARGS="--ply 2 --k-top 0 --steps 10 --warmup 2 --desync-steps 60 --timing-steps 1 --two-ply-steps 0 --kall-steps 0 --config1-steps 0 --config2-steps 0 --no-cpu-baseline"; RX="movegen|mlp_kernel"
+    ARGS="--full --ply 2 --k-top 0 --steps 10 --warmup 2 --desync-steps 60 --timing-steps 1 --two-ply-steps 0 --kall-steps 0 --config1-steps 0 --config2-steps 0 --no-cpu-baseline"; RX="movegen|mlp_kernel"
   fi
   for c in FETCH_SIZE WRITE_SIZE; do
     echo "[pmc] $P$leg $c"

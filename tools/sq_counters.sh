@@ -7,11 +7,11 @@ export TMPDIR=/tmp
 OUT=gpurun_out/${1:-sq}; LEG=${2:-2ply_k4}; RX=${3:-"movegen_pool|mlp_kernel_il"}; LANES=${4:-8192}
 mkdir -p $OUT
 if [ $LEG = 2ply_k4 ]; then
-  ARGS="--ply 2 --k-top 4 --steps 30 --warmup 10 --timing-steps 1 --two-ply-steps 0 --kall-steps 0 --config1-steps 0 --config2-steps 0 --no-cpu-baseline"
+  ARGS="--full --ply 2 --k-top 4 --steps 30 --warmup 10 --timing-steps 1 --two-ply-steps 0 --kall-steps 0 --config1-steps 0 --config2-steps 0 --no-cpu-baseline"
 elif [ $LEG = 2ply_kall ]; then
-  ARGS="--ply 2 --k-top 0 --steps 6 --warmup 2 --desync-steps 30 --timing-steps 1 --two-ply-steps 0 --kall-steps 0 --config1-steps 0 --config2-steps 0 --no-cpu-baseline"
+  ARGS="--full --ply 2 --k-top 0 --steps 6 --warmup 2 --desync-steps 30 --timing-steps 1 --two-ply-steps 0 --kall-steps 0 --config1-steps 0 --config2-steps 0 --no-cpu-baseline"
 else
-  ARGS="--steps 300 --warmup 100 --timing-steps 1 --two-ply-steps 0 --kall-steps 0 --config1-steps 0 --config2-steps 0 --no-cpu-baseline"
+  ARGS="--full --steps 300 --warmup 100 --timing-steps 1 --two-ply-steps 0 --kall-steps 0 --config1-steps 0 --config2-steps 0 --no-cpu-baseline"
 fi
 if [ $LANES != 8192 ]; then ARGS="$ARGS --lanes $LANES"; N=l${LANES}_$LEG; else N=$LEG; fi
 i=0
