@@ -105,6 +105,15 @@ int bgx_value(const bgx_net* net, const float* d_x, int n, float* d_out, void* s
 int bgx_value_boards(const bgx_net* net, const uint8_t* d_boards, const uint8_t* d_player, int n,
                      float* d_out, void* stream);
 
+/* bgx_value_boards with a network per board: d_net[i] in {0, 1} (u8) selects
+ * net0 or net1 for board i (only bit 0 is read). The rows are sorted into one
+ * index list per network and evaluated by the match mode's routed MFMA launch
+ * (the parity hook of that kernel; also: one batch of positions scored under
+ * two checkpoints). Each V has the bits bgx_value_boards gives under the
+ * board's own network. Same input-domain check as bgx_value_boards. */
+int bgx_value_boards_routed(const bgx_net* net0, const bgx_net* net1, const uint8_t* d_boards,
+                            const uint8_t* d_player, const uint8_t* d_net, int n, float* d_out, void* stream);
+
 /* compute_weighted_opponent_response (multi/two_ply.py:93-150) in exact mode
  * (no random.sample of 1-1/2-2/3-3 replies): for n afterstates d_boards and
  * the player to reply d_opponent, d_out[i] = sum over the 21 rolls of
@@ -172,6 +181,35 @@ int bgx_engine_destroy(bgx_engine* e);
  * in bgx_net_create, the sampling temperature and the parameter version. */
 int bgx_set_weights(bgx_engine* e, const float* h_W1, const float* h_b1, const float* h_w2,
                     const float* h_b2, float temperature, uint64_t version);
+
+/* Match mode: two networks head to head (which of two checkpoints plays
+ * better?). Network 0 is the one bgx_set_weights sets; network 1, the
+ * opponent, is set here. In episode k (the lane's episode counter, the header's
+ * episode no.) of global lane g, player p is played by network (p ^ g ^ k) & 1:
+ * the sides swap from lane to lane and from game to game, so each network
+ * plays PLAYER1 in half the games. At a lane's step the mover's network
+ * evaluates everything the step needs: the lane row (the record's V(s)), every
+ * candidate (V(a)) and, at ply 2, the opponent's replies to its candidates
+ * (two_ply.py:93-150 models the opponent with the mover's own network).
+ * Temperature and greedy stay per engine. Records and headers keep their
+ * layout; who played which side follows from (lane, episode no.) in the header.
+ *
+ * bgx_engine_set_opponent uploads network 1 and enters match mode; every lane
+ * restarts from BackgammonEnv.reset (as bgx_engine_set_dice), so every
+ * harvested game is a match game (episodes not yet harvested are dropped).
+ * All-null weights leave match mode and again restart the lanes (a no-op
+ * outside match mode). A later call with weights while in match mode only
+ * replaces network 1: it waits for the engine's stream, like bgx_set_weights,
+ * and does not restart. Match mode needs the phased engine (fused = 0, or
+ * ply = 2): BGX_E_STATE on a fused engine, and on an engine created with the
+ * opt-in BGX_REPLY_DELTA path (its replies would start from the wrong
+ * network's root accumulators). With BGX_GRAPH=1 a match engine launches
+ * directly and captures no graph. In match mode the step's rows are sorted by
+ * network and evaluated by one routed launch per phase (bgx_match.hip); the
+ * 2-ply gap rows (bgx_stats.gap_rows) belong to no job and are then neither
+ * evaluated nor counted in value_rows. */
+int bgx_engine_set_opponent(bgx_engine* e, const float* h_W1, const float* h_b1, const float* h_w2,
+                            const float* h_b2);
 
 /* Test hook for parity replays: scripted dice. h_dice (host) holds, per lane,
  * per_lane single-die draws (1..6) that replace np.random.randint(1, 7)
@@ -277,7 +315,8 @@ int bgx_engine_peek(bgx_engine* e, int buf, void* h_out, uint64_t bytes, uint64_
  * enabled): total milliseconds and launch counts of the movegen and MLP
  * kernels since the last reset. A fused engine (bgx_config.fused, 1-ply)
  * reports its one step kernel (all n_steps of a bgx_step) in the movegen slot
- * and 0 MLP launches. */
+ * and 0 MLP launches. In match mode an MLP slot entry is one phase's routing
+ * kernel plus its routed launch. */
 int bgx_set_timing(bgx_engine* e, int enabled);
 int bgx_get_timing(bgx_engine* e, double* ms_movegen, int* n_movegen, double* ms_mlp, int* n_mlp);
 

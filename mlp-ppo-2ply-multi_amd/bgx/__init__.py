@@ -6,6 +6,7 @@ Public surface:
   bgx.episodes harvested records -> reference-shaped Episode / Experience objects
   bgx.dist     one-process-per-GPU sharding, RCCL episode gather / weight broadcast
   bgx.records  the harvest wire format (numpy only)
+  bgx.match    two networks head to head: play(a, b, games), tally(headers); python -m bgx.match
 
 The re-exports below load on first use (PEP 562), so `import bgx.records`
 (the CPU-side queue's wire format) pulls in neither torch nor libbgx.so.
@@ -17,7 +18,7 @@ _EXPORTS = {
     "Engine": ".engine", "Harvest": ".engine",
     "BackgammonPolicyNetwork": ".net",
 }
-_SUBMODULES = ("ops", "dist", "episodes", "records", "trainer", "net", "engine")
+_SUBMODULES = ("ops", "dist", "episodes", "records", "trainer", "net", "engine", "match")
 
 __all__ = list(_EXPORTS) + ["ops"]
 

@@ -63,6 +63,9 @@ SIGNATURES = {
     "bgx_net_destroy": (c_int, [c_void_p]),
     "bgx_value": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "bgx_value_boards": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "bgx_value_boards_routed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                        c_void_p]),
+    "bgx_engine_set_opponent": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bgx_two_ply": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "bgx_two_ply_sampled": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_u64, c_void_p, c_void_p]),
     "bgx_config_default": (None, [ctypes.POINTER(Config)]),

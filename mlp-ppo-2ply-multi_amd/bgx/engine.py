@@ -83,6 +83,19 @@ class Engine:
                                     int(version)), "bgx_set_weights")
         self.version, self.temperature = int(version), float(temperature)
 
+    def set_opponent(self, weights):
+        """Match mode (bgx_engine_set_opponent, bgx/match.py): `weights` become
+        network 1, the opponent of the network set_weights sets; player p of
+        episode k on global lane g is played by network (p ^ g ^ k) & 1. Every
+        lane restarts on entering; None leaves match mode (and restarts again).
+        Phased engines only (fused=False, or ply=2)."""
+        if weights is None:
+            check(lib().bgx_engine_set_opponent(self._h, None, None, None, None), "bgx_engine_set_opponent")
+            return
+        W1, b1, w2, b2 = weights_from(weights)
+        fp = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        check(lib().bgx_engine_set_opponent(self._h, fp(W1), fp(b1), fp(w2), fp(b2)), "bgx_engine_set_opponent")
+
     def set_dice(self, dice):
         """Test hook (bgx_engine_set_dice): scripted single-die draws, uint8
         [lanes, k] in 1..6, two per roll, replacing np.random.randint(1, 7)

@@ -208,6 +208,21 @@ class Net:
         return out
 
 
+def value_boards_routed(net0, net1, boards, player, net_id, stream=None):
+    """value_boards with a network per board (bgx_value_boards_routed): net_id
+    uint8 [n] in {0, 1} picks net0 or net1 (two Net objects) for each board.
+    The match mode's routed MFMA launch; each V has the bits
+    Net.value_boards gives under the board's own network."""
+    boards, player, net_id = _u8(boards).view(-1, 52), _u8(player).view(-1), _u8(net_id).view(-1)
+    require_cuda(boards, player, net_id)
+    if net_id.shape[0] != boards.shape[0]:
+        raise ValueError("net_id must hold one entry per board")
+    out = torch.empty((boards.shape[0],), dtype=torch.float32, device=boards.device)
+    check(lib().bgx_value_boards_routed(net0._h, net1._h, ptr(boards), ptr(player), ptr(net_id), boards.shape[0],
+                                        ptr(out), stream_handle(stream)), "bgx_value_boards_routed")
+    return out
+
+
 def load_pth(path):
     """A reference checkpoint (torch.save of BackgammonPolicyNetwork.state_dict(),
     parameter_manager.py:115-151: fc1.weight / fc1.bias / value_head.weight /

@@ -109,6 +109,17 @@ struct bgx_engine {
                                     // candidate, from the root launch; K = 4: the chosen rows, own launch)
     float* zv = nullptr;            // K = 4: that launch's V output (unused)
     int jobs_cap = 0, reply_cap = 0, cand_cap = 0;
+    // match mode (bgx_engine_set_opponent): network 1, the row-index lists of the
+    // routed launches (root: L + cand_cap entries each; reply: reply_cap each),
+    // the network of each 2-ply reply root slot, and the step's routing counters
+    // (EngineDev::match_ctr); allocated on first entering match mode
+    bool match = false;
+    bgx_net* net1 = nullptr;
+    int32_t* m_list[2] = {nullptr, nullptr};
+    int32_t* m_rlist[2] = {nullptr, nullptr};
+    uint8_t* m_slot = nullptr;
+    int m_slots = 0;
+    unsigned* m_ctr = nullptr;
     int32_t* ovf_list = nullptr;
     int ovf_cap = 0;
     uint32_t* ws = nullptr;
@@ -232,6 +243,8 @@ struct Scratch {
     uint32_t* ws = nullptr;        // movegen fallback workspace (lazy)
     uint32_t* packed = nullptr;    // bgx_value_boards packed boards (lazy, grows)
     size_t packed_n = 0;
+    int32_t* lists = nullptr;      // bgx_value_boards_routed: two row-index lists of lists_n entries (lazy, grows)
+    size_t lists_n = 0;
 };
 
 constexpr int SC_OVF_CAP = 1 << 16, SC_WS_WAVES = 256, SC_WS_SLOTS = 16384;
@@ -841,6 +854,58 @@ int bgx_value_boards(const bgx_net* cnet, const uint8_t* d_boards, const uint8_t
     });
 }
 
+int bgx_value_boards_routed(const bgx_net* net0, const bgx_net* net1, const uint8_t* d_boards,
+                            const uint8_t* d_player, const uint8_t* d_net, int n, float* d_out, void* stream) {
+    return guarded("bgx_value_boards_routed", [&]() -> int {
+        if (!net0 || !net1 || n < 0) return fail(BGX_E_ARG, "bgx_value_boards_routed: bad arguments");
+        if (n == 0) return BGX_OK;
+        if (!d_boards || !d_player || !d_net || !d_out) return fail(BGX_E_ARG, "bgx_value_boards_routed: null pointer");
+        DeviceScope ds(d_boards);
+        HIP_TRY(ds.err);
+        hipStream_t s = (hipStream_t)stream;
+        Lease L;
+        if (int rc = lease_scratch(s, L)) return rc;
+        if (int rc = require_domain("bgx_value_boards_routed", L.sc, d_boards, d_player, nullptr, n, s)) return rc;
+        if (L.sc->packed_n < (size_t)n) {   // the lease's last user has finished (lease_scratch)
+            hipFree(L.sc->packed);
+            L.sc->packed = nullptr;
+            L.sc->packed_n = 0;
+            if (dalloc(&L.sc->packed, (size_t)n * 8)) return BGX_E_HIP;
+            L.sc->packed_n = (size_t)n;
+        }
+        if (L.sc->lists_n < (size_t)n) {
+            hipFree(L.sc->lists);
+            L.sc->lists = nullptr;
+            L.sc->lists_n = 0;
+            if (dalloc(&L.sc->lists, (size_t)n * 2)) return BGX_E_HIP;
+            L.sc->lists_n = (size_t)n;
+        }
+        unsigned* ctr = L.sc->words + 8;   // [0..1] list lengths, [2..3] tile claims
+        HIP_TRY(hipMemsetAsync(ctr, 0, 16, s));
+        HIP_TRY(bgx_launch_pack(d_boards, d_player, n, L.sc->packed, s));
+        bgx::MatchMlpArgs m{};
+        m.rows = L.sc->packed;
+        m.out = d_out;
+        m.n_max = n;
+        m.list_cap = n;
+        m.nt = 1;
+        m.n_hint = n;
+        const bgx_net* nets[2] = {net0, net1};
+        for (int k = 0; k < 2; ++k) {
+            m.list[k] = L.sc->lists + (size_t)k * L.sc->lists_n;
+            m.count[k] = ctr + k;
+            m.claim[k] = ctr + 2 + k;
+            m.wfrag[k] = nets[k]->wfrag;
+            m.rowc[k] = nets[k]->rowc;
+            m.b2[k] = nets[k]->b2;
+            m.feat_scale[k] = nets[k]->feat_scale;
+        }
+        HIP_TRY(bgx_launch_route_ids(d_net, n, L.sc->lists, L.sc->lists + L.sc->lists_n, ctr, s));
+        HIP_TRY(bgx_launch_mlp_routed(&m, s));
+        return BGX_OK;
+    });
+}
+
 int bgx_two_ply(const bgx_net* net, const uint8_t* d_boards, const uint8_t* d_opponent, int n,
                 double* d_out, void* stream) {
     return guarded("bgx_two_ply", [&]() -> int {
@@ -1121,7 +1186,8 @@ int bgx_engine_destroy(bgx_engine* e) {
                       e->out_records[1], e->out_records[2], e->out_headers[0], e->out_headers[1], e->out_headers[2],
                       e->d_offs[0], e->d_offs[1], e->d_offs[2], e->d_info[2], e->fh_ctr, e->d.hring, e->d.hepi,
                       e->d_info[0], e->d_info[1], e->fcand, e->fvbuf, e->ft1cnt, e->d.player, e->d.dice, e->d.step, e->d.flags, e->d.epi, e->d.rng,
-                      e->d.rec_count, e->d.ep_first, e->d.harv, e->d.ring, e->d.ep_list, e->dice_tab};
+                      e->d.rec_count, e->d.ep_first, e->d.harv, e->d.ring, e->d.ep_list, e->dice_tab,
+                      e->m_list[0], e->m_list[1], e->m_rlist[0], e->m_rlist[1], e->m_slot, e->m_ctr};
         for (void* p : ps) hipFree(p);
         for (hipEvent_t ev : e->ev) hipEventDestroy(ev);
         if (e->gexec) hipGraphExecDestroy(e->gexec);
@@ -1131,6 +1197,7 @@ int bgx_engine_destroy(bgx_engine* e) {
         if (e->h_info) hipHostFree(e->h_info);
         if (e->cap) hipStreamDestroy(e->cap);
         bgx_net_destroy(e->net);
+        bgx_net_destroy(e->net1);
         delete e;
         return BGX_OK;
     });
@@ -1307,6 +1374,7 @@ int bgx_engine_create(int device, const bgx_config* cfg, bgx_engine** out) {
         d.n_jobs2 = cfg->k_top == 4 ? L * 4 * 21 : 0;
         d.stats = e->stats;
         d.err_flags = e->ctr + C_ERR;
+        d.match_ctr = nullptr;
         if (bgx_launch_engine_reset(&d, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
             bgx_engine_destroy(e);
             return fail(BGX_E_HIP, "engine reset failed");
@@ -1368,6 +1436,73 @@ int bgx_set_weights(bgx_engine* e, const float* h_W1, const float* h_b1, const f
     });
 }
 
+// every lane restarts from BackgammonEnv.reset (as bgx_engine_set_dice): entering
+// or leaving match mode, so that every harvested game was played in one mode
+static int restart_lanes(bgx_engine* e) {
+    if (e->gexec) {
+        HIP_TRY(hipGraphExecDestroy(e->gexec));
+        e->gexec = nullptr;
+    }
+    HIP_TRY(hipMemset(e->ctr, 0, 64));
+    HIP_TRY(bgx_launch_engine_reset(&e->d, nullptr));
+    e->t1_ready = false;
+    HIP_TRY(hipDeviceSynchronize());
+    return check_flags(e);
+}
+
+int bgx_engine_set_opponent(bgx_engine* e, const float* h_W1, const float* h_b1, const float* h_w2,
+                            const float* h_b2) {
+    return guarded("bgx_engine_set_opponent", [&]() -> int {
+        if (!e) return fail(BGX_E_ARG, "bgx_engine_set_opponent: null engine");
+        const bool none = !h_W1 && !h_b1 && !h_w2 && !h_b2;
+        if (!none && (!h_W1 || !h_b1 || !h_w2 || !h_b2))
+            return fail(BGX_E_ARG, "bgx_engine_set_opponent: all four weight arrays, or all null to leave match mode");
+        if (e->fused)
+            return fail(BGX_E_STATE, "bgx_engine_set_opponent: match mode needs the phased engine (fused = 0 or ply = 2)");
+        if (e->zt)
+            return fail(BGX_E_STATE, "bgx_engine_set_opponent: match mode does not combine with BGX_REPLY_DELTA (the "
+                                     "replies would start from the wrong network's root accumulators)");
+        HIP_TRY(hipSetDevice(e->device));
+        if (e->last) HIP_TRY(hipStreamSynchronize(e->last));
+        if (none) {
+            if (!e->match) return BGX_OK;
+            e->match = false;
+            e->d.match_ctr = nullptr;
+            return restart_lanes(e);
+        }
+        if (e->match) return net_upload(e->net1, h_W1, h_b1, h_w2, h_b2);   // replace network 1: no restart
+        if (!e->net1) {
+            if (int rc = bgx_net_create(h_W1, h_b1, h_w2, h_b2, &e->net1)) return rc;
+        } else if (int rc = net_upload(e->net1, h_W1, h_b1, h_w2, h_b2)) {
+            return rc;
+        }
+        if (!e->m_ctr) {
+            const size_t root_n = (size_t)e->cfg.lanes + (size_t)e->cand_cap;
+            int rc = BGX_OK;
+            // (a pointer already set is from an earlier attempt that ran out of memory later)
+            for (int n = 0; n < 2 && !rc; ++n) {
+                if (!e->m_list[n]) rc = dalloc(&e->m_list[n], root_n);
+                if (!rc) HIP_TRY(hipMemset(e->m_list[n], 0xFF, root_n * 4));   // -1: an empty row
+                if (!rc && e->cfg.ply == 2) {
+                    if (!e->m_rlist[n]) rc = dalloc(&e->m_rlist[n], (size_t)e->reply_cap);
+                    if (!rc) HIP_TRY(hipMemset(e->m_rlist[n], 0xFF, (size_t)e->reply_cap * 4));
+                }
+            }
+            if (!rc && e->cfg.ply == 2) {
+                e->m_slots = e->cfg.k_top == 4 ? 4 * e->cfg.lanes : e->cand_cap;
+                if (!e->m_slot) rc = dalloc(&e->m_slot, (size_t)e->m_slots);
+                if (!rc) HIP_TRY(hipMemset(e->m_slot, 0, (size_t)e->m_slots));
+            }
+            if (!rc) rc = dalloc(&e->m_ctr, 8);
+            if (rc) return rc;
+        }
+        HIP_TRY(hipMemset(e->m_ctr, 0, 32));
+        e->match = true;
+        e->d.match_ctr = e->m_ctr;
+        return restart_lanes(e);
+    });
+}
+
 static void mg_common(bgx_engine* e, bgx::MovegenArgs& a) {
     a.ovf_count = e->ctr + C_OVF;
     a.ovf_zeroed = 1;   // the per-step memset covers it
@@ -1388,6 +1523,63 @@ static int timed(bgx_engine* e, int kind, hipStream_t s, bool start) {
     e->ev.push_back(ev);
     e->ev_kind.push_back(start ? kind : -1);
     return BGX_OK;
+}
+
+// match mode: the routing kernels' arguments (root and reply launch share them)
+static bgx::MatchRouteArgs match_route_args(bgx_engine* e) {
+    const int L = e->cfg.lanes;
+    bgx::MatchRouteArgs a{};
+    a.L = L;
+    a.lane_base = e->cfg.lane_base;
+    a.cand_cap = e->cand_cap;
+    a.player = e->d.player;
+    a.epi = e->d.epi;
+    a.cand_off = e->cand_off;
+    a.cand_cnt = e->cand_cnt;
+    a.flat_count = e->ctr + C_FLAT;
+    a.list[0] = e->m_list[0];
+    a.list[1] = e->m_list[1];
+    a.count = e->m_ctr;
+    a.slot_net = e->m_slot;
+    a.k_top = e->cfg.k_top;
+    a.n_slots = e->m_slots;
+    if (e->cfg.ply == 2) {
+        if (e->cfg.k_top == 4) {
+            a.n_jobs = L * 4 * 21;
+        } else {
+            a.n_units_dev = e->ctr + C_FLAT;
+            a.n_jobs_max = e->jobs_cap;
+        }
+        a.job_off = e->job_off;
+        a.job_cnt = e->job_cnt;
+        a.reply_cap = e->reply_cap;
+        a.rlist[0] = e->m_rlist[0];
+        a.rlist[1] = e->m_rlist[1];
+        a.rcount = e->m_ctr + 2;
+    }
+    return a;
+}
+
+// ... and a routed launch's: the root launch (lane rows + candidates, one tile
+// per wave iteration) or the 2-ply reply launch (two tiles)
+static bgx::MatchMlpArgs match_mlp_args(bgx_engine* e, bool reply) {
+    bgx::MatchMlpArgs m{};
+    m.rows = reply ? e->reply_rows : e->rows;
+    m.out = reply ? e->reply_V : e->V;
+    m.n_max = reply ? e->reply_cap : e->cfg.lanes + e->cand_cap;
+    m.list_cap = m.n_max;
+    m.nt = reply ? 2 : 1;
+    const bgx_net* nets[2] = {e->net, e->net1};
+    for (int n = 0; n < 2; ++n) {
+        m.list[n] = reply ? e->m_rlist[n] : e->m_list[n];
+        m.count[n] = e->m_ctr + (reply ? 2 : 0) + n;
+        m.claim[n] = e->m_ctr + (reply ? 6 : 4) + n;
+        m.wfrag[n] = nets[n]->wfrag;
+        m.rowc[n] = nets[n]->rowc;
+        m.b2[n] = nets[n]->b2;
+        m.feat_scale[n] = nets[n]->feat_scale;
+    }
+    return m;
 }
 
 // the per-step launch sequence (captured into a graph by bgx_step)
@@ -1428,7 +1620,14 @@ static int enqueue_steps(bgx_engine* e, int n_steps, hipStream_t s) {
             m.z_base = L;
         }
         if (timed(e, 1, s, true)) return BGX_E_HIP;
-        HIP_TRY(bgx_launch_mlp(&m, s));
+        if (e->match) {   // rows sorted by the mover's network, then one routed launch
+            const bgx::MatchRouteArgs ra = match_route_args(e);
+            HIP_TRY(bgx_launch_route_root(&ra, s));
+            const bgx::MatchMlpArgs mm = match_mlp_args(e, false);
+            HIP_TRY(bgx_launch_mlp_routed(&mm, s));
+        } else {
+            HIP_TRY(bgx_launch_mlp(&m, s));
+        }
         if (timed(e, 1, s, false)) return BGX_E_HIP;
 
         if (e->cfg.ply == 2) {
@@ -1501,7 +1700,14 @@ static int enqueue_steps(bgx_engine* e, int n_steps, hipStream_t s) {
                 r.n_slots = r.n_roots;
             }
             if (timed(e, 1, s, true)) return BGX_E_HIP;
-            HIP_TRY(bgx_launch_mlp(&r, s));
+            if (e->match) {   // each job's rows to the list of its root slot's network
+                const bgx::MatchRouteArgs ra = match_route_args(e);
+                HIP_TRY(bgx_launch_route_reply(&ra, s));
+                const bgx::MatchMlpArgs mm = match_mlp_args(e, true);
+                HIP_TRY(bgx_launch_mlp_routed(&mm, s));
+            } else {
+                HIP_TRY(bgx_launch_mlp(&r, s));
+            }
             if (timed(e, 1, s, false)) return BGX_E_HIP;
             // reference-sampled mode (cfg.reply_sample > 0): keyed by the seed and the
             // lane block, salted per step by the engine's env-step counter
@@ -1596,7 +1802,8 @@ int bgx_step(bgx_engine* e, int n_steps, void* stream) {
         // n_steps sequence is one graph launch (kernel arguments are fixed for the
         // engine's lifetime; bgx_set_weights drops the graph: temperature is an argument)
         if (e->fused) return enqueue_fused(e, n_steps, s);
-        if (e->timing || !e->use_graph) return enqueue_steps(e, n_steps, s);
+        // (a match engine launches directly too: no graph is captured in match mode)
+        if (e->timing || !e->use_graph || e->match) return enqueue_steps(e, n_steps, s);
         if (!e->gexec || e->g_steps != n_steps) {
             if (e->gexec) {
                 HIP_TRY(hipGraphExecDestroy(e->gexec));

@@ -63,6 +63,14 @@ __global__ __launch_bounds__(256) void select_step_kernel(EngineDev e) {
             atomicAdd(e.stats + 6, (unsigned long long)*e.reply_count);   // reply rows (gaps included)
             jobs += e.k_top == 0 ? 21ull * fc : (unsigned long long)e.n_jobs2;
         }
+        if (e.match_ctr) {
+            // match mode: the rows the routed launches evaluated (the two root
+            // lists, the two reply lists; gap rows are on no list); the routing
+            // counters and tile claims are zeroed for the next step
+            rows = 0;
+            for (int k = 0; k < 4; ++k) rows += e.match_ctr[k];
+            for (int k = 0; k < 8; ++k) e.match_ctr[k] = 0u;
+        }
         atomicAdd(e.stats + 0, (unsigned long long)e.L);
         atomicAdd(e.stats + 3, rows);
         atomicAdd(e.stats + 4, jobs);

@@ -153,6 +153,59 @@ struct EngineDev {
     int n_jobs2;                 // 2-ply jobs this step when k_top = 4
     unsigned long long* stats;   // [8] env steps, decisions, episodes, value rows, movegen jobs, fallback
     unsigned* err_flags;
+    // match mode (bgx_engine_set_opponent; null otherwise): the step's routing
+    // counters, [0..1] root list lengths, [2..3] reply list lengths, [4..7] the
+    // routed launches' tile claims. The step kernel counts the routed rows as
+    // the step's value rows and zeroes all eight for the next step.
+    unsigned* match_ctr;
+};
+
+// Match mode (bgx_match.hip): the two sides of every game are played by two
+// networks. A routed launch evaluates rows[idx] for the indices of two lists,
+// list n under network n, and stores out[idx]; an index outside [0, n_max) is
+// an empty row (nothing stored).
+struct MatchMlpArgs {
+    const uint32_t* rows;        // packed boards [n_max][8]
+    float* out;                  // [n_max] V
+    int n_max;                   // rows / out capacity: the bound of every index
+    int list_cap;                // entries each list holds (a device count above it is clamped)
+    int nt;                      // 32-board tiles per wave iteration: 1 or 2
+    int n_hint;                  // > 0: the host knows there are at most this many rows in all (grid size)
+    const int32_t* list[2];      // row indices per network
+    const unsigned* count[2];    // list lengths (device)
+    unsigned* claim[2];          // tile claim counters (zero at launch)
+    const uint4* wfrag[2];       // per network: split-fp16 fragments, w2, b2, 2^-e (MlpArgs)
+    const float* rowc[2];
+    float b2[2];
+    float feat_scale[2];
+};
+
+// Root routing (one thread per lane): lane l's network n = (player ^ global
+// lane ^ episode) & 1 takes the lane row l and the candidate rows L + cand_off[l]
+// .. (clamped to the rows the flat buffer holds); ply 2: the network of each
+// reply root slot (K = all: per candidate row; K = 4: slots 4 l .. 4 l + 3).
+// Reply routing (one thread per job): job j's rows go to the list of slot_net[j / 21].
+struct MatchRouteArgs {
+    int L, lane_base, cand_cap;
+    const uint8_t* player;
+    const uint32_t* epi;
+    const int32_t* cand_off;
+    const int32_t* cand_cnt;
+    const unsigned* flat_count;  // candidate rows this step
+    int32_t* list[2];            // root lists, L + cand_cap entries each
+    unsigned* count;             // [2]
+    uint8_t* slot_net;           // ply 2: [cand_cap] (K = all) or [4 L] (K = 4); else null
+    int k_top;
+    // reply routing
+    int n_jobs;                  // host job count (K = 4), else 21 x *n_units_dev clamped to n_jobs_max
+    const unsigned* n_units_dev;
+    int n_jobs_max;
+    int n_slots;                 // entries of slot_net
+    const int32_t* job_off;
+    const int32_t* job_cnt;
+    int reply_cap;               // reply rows buffer / reply list capacity
+    int32_t* rlist[2];
+    unsigned* rcount;            // [2]
 };
 
 // Fused 1-ply lane step (bgx_fused.hip): one persistent launch runs n_steps
@@ -241,6 +294,12 @@ extern "C" {
 hipError_t bgx_launch_movegen(const bgx::MovegenArgs* args, hipStream_t stream);
 hipError_t bgx_launch_mlp(const bgx::MlpArgs* args, hipStream_t stream);
 hipError_t bgx_launch_fused(const bgx::FusedArgs* args, hipStream_t stream);
+hipError_t bgx_launch_mlp_routed(const bgx::MatchMlpArgs* args, hipStream_t stream);
+hipError_t bgx_launch_route_root(const bgx::MatchRouteArgs* args, hipStream_t stream);
+hipError_t bgx_launch_route_reply(const bgx::MatchRouteArgs* args, hipStream_t stream);
+// ids[i] in {0, 1} -> two index lists (stateless bgx_value_boards_routed); ctr[0..1] the counts
+hipError_t bgx_launch_route_ids(const uint8_t* ids, int n, int32_t* list0, int32_t* list1, unsigned* ctr,
+                                hipStream_t stream);
 // input-domain check (flags[0] = BGX_BADF_* bits, flags[1] = first bad index)
 hipError_t bgx_launch_validate(const uint8_t* boards, const uint8_t* player, const uint8_t* dice, int n,
                                unsigned* flags, hipStream_t stream);
