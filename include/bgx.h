@@ -220,6 +220,62 @@ int bgx_engine_set_opponent(bgx_engine* e, const float* h_W1, const float* h_b1,
  * bgx_sync / bgx_harvest (the roll is then 1-2). */
 int bgx_engine_set_dice(bgx_engine* e, const uint8_t* h_dice, int per_lane);
 
+/* Rollout mode: play given positions out instead of whole games. h_boards
+ * (host) holds n_pos boards u8[52] (positions_0[24] | positions_1[24] | bar[2] |
+ * off[2]), h_player the player on roll of each (0 / 1), h_dice two bytes per
+ * position: 0, 0 = the first roll is rolled, else the dice to play first
+ * (NULL: 0, 0 everywhere). While the table is set, global lane g = lane_base +
+ * i plays position g % n_pos in every one of its episodes: a restart loads the
+ * position's board and player on roll, with no starter roll, and is otherwise
+ * the usual one (steps 0, shaping and decided flags 0, episode no. + 1). The
+ * first roll of episode k on lane g is, in this order: the position's dice if
+ * non-zero; else, with strat_stride > 0, the stratified roll of trial t = k *
+ * strat_stride + g / n_pos, (d0, d1) = ((t % 36) / 6 + 1, (t % 36) % 6 + 1)
+ * (over strat_stride * G trials per position with strat_stride * G % 36 == 0
+ * every position sees each of the 36 ordered rolls equally often); else one
+ * roll from the lane's stream, doubles allowed (a mid-game roll; with scripted
+ * dice the lane's next two draws). Only the last form consumes a draw.
+ *
+ * The call waits for the engine's stream, uploads the table and restarts every
+ * lane (episodes not yet harvested are dropped, as with
+ * bgx_engine_set_opponent). n_pos = 0 with null pointers leaves rollout mode
+ * and restarts the lanes from BackgammonEnv.reset (a no-op outside the mode).
+ * It composes with match mode (the seat rule (p ^ g ^ k) & 1 is untouched),
+ * scripted dice (either may be set first; both restart the lanes), ply 2 and
+ * greedy or sampled move choice. BGX_E_STATE on a fused engine. BGX_E_ARG, with
+ * the first offending index in the message and before anything is uploaded,
+ * for a board outside the input domain above (bgx_check_boards_host), a player
+ * without exactly 15 checkers (points + bar + off), a position that is already
+ * over (15 off), a player byte other than 0 / 1, or a dice pair that is neither
+ * 0, 0 nor two values in 1..6.
+ *
+ * From a given position an episode can be a single env step long, while
+ * bgx_engine_create derives ep_cap from games of at least 13 env steps. A
+ * rollout caller therefore harvests at least every ep_cap / lanes steps, or
+ * creates the engine with cfg.ep_cap >= lanes * (steps between harvests); an
+ * overflow of the episode list is BGX_E_CAPACITY, as ever. */
+int bgx_engine_set_start(bgx_engine* e, const uint8_t* h_boards /* [n_pos][52] */,
+                         const uint8_t* h_player /* [n_pos] */, const uint8_t* h_dice /* [n_pos][2] or NULL */,
+                         int n_pos, uint32_t strat_stride);
+
+/* The rollout tally: d_counts[pos][8] (u64, device) += the results of the
+ * n_headers episode headers at d_headers (device; a harvest's d_headers), pos =
+ * header lane % n_pos, seen from the player on roll at the start
+ * (d_start_player[pos], device): words 0..2 regular / gammon / backgammon wins
+ * of the player on roll, 3..5 the same for the other player, 6 unfinished games
+ * (win type 0: the game hit max_steps), 7 the sum of the headers' env steps.
+ * Headers with episode no. >= max_episode are skipped. The kernel only adds: the
+ * caller zeroes d_counts once and calls accumulate; all integer, so the totals
+ * do not depend on the order. Stateless and asynchronous on `stream`: no
+ * synchronization and no allocation, so it can run on a harvest ticket's arrays
+ * before the second harvest after it. d_headers must be 16-byte aligned (the
+ * kernel reads a header as 16-byte words; a harvest's d_headers is), d_counts
+ * 8-byte aligned. BGX_E_ARG for null pointers with
+ * n_headers > 0, n_headers < 0 or n_pos <= 0; n_headers == 0 is BGX_OK with no
+ * launch. */
+int bgx_rollout_tally(const uint32_t* d_headers, int n_headers, const uint8_t* d_start_player, int n_pos,
+                      uint32_t max_episode, uint64_t* d_counts, void* stream);
+
 /* Advance every lane by n_steps env steps (one BackgammonEnv.step each,
  * passes included; finished games are recorded and the lane restarts); with
  * cfg.balance, n_steps x lanes lane-steps in total (bgx_get_stats counts them). */

@@ -7,6 +7,8 @@ Public surface:
   bgx.dist     one-process-per-GPU sharding, RCCL episode gather / weight broadcast
   bgx.records  the harvest wire format (numpy only)
   bgx.match    two networks head to head: play(a, b, games), tally(headers); python -m bgx.match
+  bgx.rollout  play given positions out: rollout(weights, boards, player), summarize(counts);
+               python -m bgx.rollout
 
 The re-exports below load on first use (PEP 562), so `import bgx.records`
 (the CPU-side queue's wire format) pulls in neither torch nor libbgx.so.
@@ -18,7 +20,7 @@ _EXPORTS = {
     "Engine": ".engine", "Harvest": ".engine",
     "BackgammonPolicyNetwork": ".net",
 }
-_SUBMODULES = ("ops", "dist", "episodes", "records", "trainer", "net", "engine", "match")
+_SUBMODULES = ("ops", "dist", "episodes", "records", "trainer", "net", "engine", "match", "rollout")
 
 __all__ = list(_EXPORTS) + ["ops"]
 

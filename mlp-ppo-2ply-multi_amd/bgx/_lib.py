@@ -73,6 +73,8 @@ SIGNATURES = {
     "bgx_engine_destroy": (c_int, [c_void_p]),
     "bgx_set_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_u64]),
     "bgx_engine_set_dice": (c_int, [c_void_p, c_void_p, c_int]),
+    "bgx_engine_set_start": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_uint32]),
+    "bgx_rollout_tally": (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.c_uint32, c_void_p, c_void_p]),
     "bgx_step": (c_int, [c_void_p, c_int, c_void_p]),
     "bgx_sync": (c_int, [c_void_p]),
     "bgx_harvest": (c_int, [c_void_p, ctypes.POINTER(HarvestInfo), c_void_p]),

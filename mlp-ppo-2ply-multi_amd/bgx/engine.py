@@ -106,6 +106,30 @@ class Engine:
         check(lib().bgx_engine_set_dice(self._h, d.ctypes.data_as(ctypes.c_void_p), int(d.shape[1])),
               "bgx_engine_set_dice")
 
+    def set_start(self, boards, player=None, dice=None, strat_stride=0):
+        """Rollout mode (bgx_engine_set_start, bgx/rollout.py): global lane g
+        plays position g % n_pos of `boards` (uint8 [n_pos, 52]) in every
+        episode, `player` [n_pos] on roll; `dice` [n_pos, 2], 0, 0 = roll (None:
+        every first roll is rolled); strat_stride > 0: rolled first rolls are
+        the stratified ones of include/bgx.h. Every lane restarts; None leaves
+        the mode (and restarts again). Phased engines only."""
+        import numpy as np
+        if boards is None:
+            check(lib().bgx_engine_set_start(self._h, None, None, None, 0, 0), "bgx_engine_set_start")
+            return
+        if player is None:
+            raise ValueError("set_start(boards, player): `player` (the player on roll of each position) is missing")
+        b = np.ascontiguousarray(np.asarray(boards, dtype=np.uint8).reshape(-1, 52))
+        p = np.ascontiguousarray(np.asarray(player, dtype=np.uint8).reshape(-1))
+        if p.shape[0] != b.shape[0]:
+            raise ValueError(f"{b.shape[0]} boards, {p.shape[0]} players")
+        d = None
+        if dice is not None:
+            d = np.ascontiguousarray(np.broadcast_to(np.asarray(dice, dtype=np.uint8), (b.shape[0], 2)))
+        vp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        check(lib().bgx_engine_set_start(self._h, vp(b), vp(p), vp(d), int(b.shape[0]), int(strat_stride)),
+              "bgx_engine_set_start")
+
     def step(self, n=1, stream=None):
         """Advance every lane by n env steps (asynchronous on the stream);
         balance=True: n x lanes lane-steps in total, faster lanes run ahead."""

@@ -223,6 +223,27 @@ def value_boards_routed(net0, net1, boards, player, net_id, stream=None):
     return out
 
 
+def rollout_tally(headers, start_player, n_pos, max_episode, counts, stream=None):
+    """counts[pos][8] += the results of `headers` (bgx_rollout_tally; bgx/rollout.py
+    tally_counts is its numpy statement): headers int32 [n, 16] on the device (a
+    harvest's), start_player uint8 [n_pos] and counts int64 [n_pos, 8] (the bits
+    of the u64 counters) on the same device. Asynchronous on the stream; the
+    caller zeroes counts once, calls accumulate. Returns counts."""
+    require_cuda(headers, start_player, counts)   # device tensors, contiguous
+    if not (headers.device == start_player.device == counts.device):
+        raise ValueError("headers, start_player and counts must be on the same device")
+    n_pos = int(n_pos)
+    if headers.dtype != torch.int32 or headers.dim() != 2 or headers.shape[1] != 16:
+        raise ValueError("headers must be int32 [n, 16]")
+    if start_player.dtype != torch.uint8 or start_player.numel() != n_pos:
+        raise ValueError("start_player must be uint8 [n_pos]")
+    if counts.dtype != torch.int64 or counts.numel() != n_pos * 8:
+        raise ValueError("counts must be int64 [n_pos, 8]")
+    check(lib().bgx_rollout_tally(ptr(headers), int(headers.shape[0]), ptr(start_player), n_pos, int(max_episode),
+                                  ptr(counts), stream_handle(stream)), "bgx_rollout_tally")
+    return counts
+
+
 def load_pth(path):
     """A reference checkpoint (torch.save of BackgammonPolicyNetwork.state_dict(),
     parameter_manager.py:115-151: fc1.weight / fc1.bias / value_head.weight /

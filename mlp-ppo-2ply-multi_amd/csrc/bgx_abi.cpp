@@ -164,6 +164,7 @@ struct bgx_engine {
     bool prof_enabled = false;
     int fused_fl = 0;             // BGX_FUSED_LANES: fused 1-ply lanes per workgroup (16 / 32; 0 = auto)
     uint8_t* dice_tab = nullptr;  // bgx_engine_set_dice
+    uint32_t* start_tab = nullptr;   // bgx_engine_set_start (EngineDev::start_tab)
     std::vector<int> ev_kind;
     double ms_mg = 0, ms_mlp = 0;
     int n_mg = 0, n_mlp = 0;
@@ -1186,7 +1187,7 @@ int bgx_engine_destroy(bgx_engine* e) {
                       e->out_records[1], e->out_records[2], e->out_headers[0], e->out_headers[1], e->out_headers[2],
                       e->d_offs[0], e->d_offs[1], e->d_offs[2], e->d_info[2], e->fh_ctr, e->d.hring, e->d.hepi,
                       e->d_info[0], e->d_info[1], e->fcand, e->fvbuf, e->ft1cnt, e->d.player, e->d.dice, e->d.step, e->d.flags, e->d.epi, e->d.rng,
-                      e->d.rec_count, e->d.ep_first, e->d.harv, e->d.ring, e->d.ep_list, e->dice_tab,
+                      e->d.rec_count, e->d.ep_first, e->d.harv, e->d.ring, e->d.ep_list, e->dice_tab, e->start_tab,
                       e->m_list[0], e->m_list[1], e->m_rlist[0], e->m_rlist[1], e->m_slot, e->m_ctr};
         for (void* p : ps) hipFree(p);
         for (hipEvent_t ev : e->ev) hipEventDestroy(ev);
@@ -1436,8 +1437,9 @@ int bgx_set_weights(bgx_engine* e, const float* h_W1, const float* h_b1, const f
     });
 }
 
-// every lane restarts from BackgammonEnv.reset (as bgx_engine_set_dice): entering
-// or leaving match mode, so that every harvested game was played in one mode
+// every lane restarts (as bgx_engine_set_dice) from BackgammonEnv.reset, or in
+// rollout mode from its start-table position: entering or leaving match mode
+// or rollout mode, so that every harvested game was played in one mode
 static int restart_lanes(bgx_engine* e) {
     if (e->gexec) {
         HIP_TRY(hipGraphExecDestroy(e->gexec));
@@ -1500,6 +1502,80 @@ int bgx_engine_set_opponent(bgx_engine* e, const float* h_W1, const float* h_b1,
         e->match = true;
         e->d.match_ctr = e->m_ctr;
         return restart_lanes(e);
+    });
+}
+
+int bgx_engine_set_start(bgx_engine* e, const uint8_t* h_boards, const uint8_t* h_player, const uint8_t* h_dice,
+                         int n_pos, uint32_t strat_stride) {
+    return guarded("bgx_engine_set_start", [&]() -> int {
+        if (!e) return fail(BGX_E_ARG, "bgx_engine_set_start: null engine");
+        const bool none = n_pos == 0 && !h_boards && !h_player && !h_dice;
+        if (!none && (!h_boards || !h_player || n_pos <= 0))
+            return fail(BGX_E_ARG, "bgx_engine_set_start: boards and players of n_pos > 0 positions, or all null with "
+                                   "n_pos = 0 to leave rollout mode (n_pos=%d)", n_pos);
+        if (e->fused)
+            return fail(BGX_E_STATE, "bgx_engine_set_start: rollout mode needs the phased engine (fused = 0 or ply = 2)");
+        // every position is checked before anything is uploaded
+        std::vector<uint32_t> tab((size_t)(none ? 0 : n_pos) * 8);
+        for (int i = 0; i < n_pos; ++i) {
+            const uint8_t* b = h_boards + (size_t)i * 52;
+            if (const unsigned bad = bgx::domain_bits(b, (int)h_player[i], nullptr))
+                return fail(BGX_E_ARG, "bgx_engine_set_start: position %d outside the input domain (bits 0x%x: 1 shared "
+                                       "point, 2 more than 15 checkers, 4 a count above 15, 16 player not 0 / 1)", i, bad);
+            unsigned sum[2] = {(unsigned)b[48] + b[50], (unsigned)b[49] + b[51]};
+            for (int k = 0; k < 24; ++k) {
+                sum[0] += b[k];
+                sum[1] += b[24 + k];
+            }
+            if (sum[0] != 15 || sum[1] != 15)
+                return fail(BGX_E_ARG, "bgx_engine_set_start: position %d has %u and %u checkers (15 each: points + bar + "
+                                       "off)", i, sum[0], sum[1]);
+            if (b[50] >= 15 || b[51] >= 15)
+                return fail(BGX_E_ARG, "bgx_engine_set_start: position %d is already over (15 checkers off)", i);
+            const unsigned d0 = h_dice ? h_dice[2 * (size_t)i] : 0u, d1 = h_dice ? h_dice[2 * (size_t)i + 1] : 0u;
+            if (!(d0 == 0 && d1 == 0) && (d0 < 1 || d0 > 6 || d1 < 1 || d1 > 6))
+                return fail(BGX_E_ARG, "bgx_engine_set_start: position %d has dice %u, %u (0, 0 = roll, or two values in "
+                                       "1..6)", i, d0, d1);
+            uint32_t* w = tab.data() + (size_t)i * 8;
+            for (int k = 0; k < 48; ++k) w[k >> 3] |= (uint32_t)b[k] << (4 * (k & 7));
+            w[6] = (uint32_t)b[48] | (uint32_t)b[49] << 4 | (uint32_t)b[50] << 8 | (uint32_t)b[51] << 12 |
+                   (uint32_t)h_player[i] << 16;
+            w[7] = (uint32_t)h_player[i] | d0 << 8 | d1 << 16;
+        }
+        HIP_TRY(hipSetDevice(e->device));
+        if (e->last) HIP_TRY(hipStreamSynchronize(e->last));
+        if (none && !e->start_tab) return BGX_OK;
+        // the new table is complete on the device before the old one goes: a
+        // failure up to here leaves the engine in the mode and games it had
+        uint32_t* fresh = nullptr;
+        if (!none) {
+            if (int rc = dalloc(&fresh, tab.size())) return rc;
+            const hipError_t ec = hipMemcpy(fresh, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);
+            if (ec != hipSuccess) {
+                hipFree(fresh);
+                return fail(BGX_E_HIP, "bgx_engine_set_start: table upload failed: %s", hipGetErrorString(ec));
+            }
+        }
+        hipFree(e->start_tab);
+        e->start_tab = fresh;
+        e->d.start_tab = fresh;
+        e->d.n_pos = none ? 0 : n_pos;
+        e->d.strat_stride = none ? 0u : strat_stride;
+        return restart_lanes(e);
+    });
+}
+
+int bgx_rollout_tally(const uint32_t* d_headers, int n_headers, const uint8_t* d_start_player, int n_pos,
+                      uint32_t max_episode, uint64_t* d_counts, void* stream) {
+    return guarded("bgx_rollout_tally", [&]() -> int {
+        if (n_headers < 0 || n_pos <= 0 || (n_headers > 0 && (!d_headers || !d_start_player || !d_counts)))
+            return fail(BGX_E_ARG, "bgx_rollout_tally: bad arguments (n_headers=%d, n_pos=%d)", n_headers, n_pos);
+        if (n_headers == 0) return BGX_OK;
+        DeviceScope ds(d_headers);
+        HIP_TRY(ds.err);
+        HIP_TRY(bgx_launch_rollout_tally(d_headers, n_headers, d_start_player, n_pos, max_episode,
+                                         (unsigned long long*)d_counts, (hipStream_t)stream));
+        return BGX_OK;
     });
 }
 

@@ -121,6 +121,31 @@ BGX_DEV int new_game(Rng& rng, uint32_t* w, int& d0, int& d1) {
     return starter;
 }
 
+// Rollout mode (EngineDev::start_tab set): global lane g starts episode `epi` from
+// position g % n_pos of the start table, with the table's player on roll and no
+// starter roll. The first roll: the position's fixed dice if it has any; else,
+// with strat_stride > 0, the stratified roll of trial t = epi * strat_stride +
+// g / n_pos, (t % 36) / 6 + 1 and (t % 36) % 6 + 1 (neither draws from the
+// lane's stream); else one roll from the stream (doubles allowed: a mid-game roll).
+template <typename Rng>
+BGX_DEV int start_game(const EngineDev& e, int i, uint32_t epi, Rng& rng, uint32_t* w, int& d0, int& d1) {
+    const uint32_t g = (uint32_t)(e.lane_base + i), np = (uint32_t)e.n_pos;
+    load_packed(e.start_tab + (size_t)(g % np) * 8, w);
+    const uint32_t m = w[7];
+    w[7] = 0;
+    if (m >> 8) {
+        d0 = (int)((m >> 8) & 0xFFu);
+        d1 = (int)((m >> 16) & 0xFFu);
+    } else if (e.strat_stride) {
+        const uint32_t r = (uint32_t)(((uint64_t)epi * e.strat_stride + g / np) % 36u);
+        d0 = (int)(r / 6u) + 1;
+        d1 = (int)(r % 6u) + 1;
+    } else {
+        rng.roll(d0, d1);
+    }
+    return (int)(m & 1u);
+}
+
 BGX_DEV uint32_t pts_word(const uint32_t* w, int pl, int k) { return pl ? w[3 + k] : w[k]; }
 
 struct Outcome { float reward; int done, win_type, close, prime; };
@@ -223,8 +248,10 @@ BGX_DEV DiceTab lane_dice(const EngineDev& e, int i) {
 // candidate `action`, vs / va = V(s) / V(a), n_full = the full candidate count. The
 // state update runs on every calling thread (a wave keeps its lane's state
 // uniform in registers); only `lead` writes memory (record, episode header,
-// the lane's board row).
-template <typename Rng>
+// the lane's board row). Start: the lane may restart from the start table
+// (rollout mode; only the phased engine's step_lane sets it, so the fused
+// kernel's instantiations carry no trace of the mode).
+template <bool Start = false, typename Rng>
 BGX_DEV void lane_advance(const EngineDev& e, int i, LaneState& s, Rng& rng, int action, const uint32_t* nb, float vs,
                           float va, int n_full, bool lead) {
     rng.ctr = s.ctr;
@@ -292,7 +319,8 @@ BGX_DEV void lane_advance(const EngineDev& e, int i, LaneState& s, Rng& rng, int
                 atomicOr(e.err_flags, BGX_ERRF_EPISODE_LIST);
             }
         }
-        s.p = new_game(rng, s.w, s.d0, s.d1);
+        if (Start && e.start_tab) s.p = start_game(e, i, s.epi + 1u, rng, s.w, s.d0, s.d1);
+        else s.p = new_game(rng, s.w, s.d0, s.d1);
         s.steps = 0;
         s.flags = 0;
         s.epi = s.epi + 1;
@@ -320,7 +348,7 @@ BGX_DEV void step_lane(const EngineDev& e, int i, int action) {
     rng.key = lane_key(e.seed, (uint32_t)(e.lane_base + i));
     rng.ctr = s.ctr;
     rng.dt = lane_dice(e, i);
-    lane_advance(e, i, s, rng, action, nb, e.V[i], act ? e.V[base + action] : 0.0f, n_full, true);
+    lane_advance<true>(e, i, s, rng, action, nb, e.V[i], act ? e.V[base + action] : 0.0f, n_full, true);
     lane_store(e, i, s);
 }
 

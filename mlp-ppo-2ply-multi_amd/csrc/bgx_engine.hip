@@ -27,7 +27,7 @@ __global__ __launch_bounds__(256) void engine_reset_kernel(EngineDev e) {
     rng.dt = lane_dice(e, i);
     uint32_t w[8];
     int d0, d1;
-    const int p = new_game(rng, w, d0, d1);
+    const int p = e.start_tab ? start_game(e, i, 0u, rng, w, d0, d1) : new_game(rng, w, d0, d1);
     if (rng.exhausted) atomicOr(e.err_flags, BGX_ERRF_DICE_EXHAUSTED);
     store_packed(e.rows + (size_t)i * 8, w);
     e.player[i] = (uint8_t)p;

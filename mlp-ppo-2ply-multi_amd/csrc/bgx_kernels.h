@@ -158,6 +158,15 @@ struct EngineDev {
     // routed launches' tile claims. The step kernel counts the routed rows as
     // the step's value rows and zeroes all eight for the next step.
     unsigned* match_ctr;
+    // rollout mode (bgx_engine_set_start; null otherwise): the start table,
+    // [n_pos][8] words per position: words 0..6 the packed board (word 6 bit 16 =
+    // the player on roll), word 7 = player on roll | dice0 << 8 | dice1 << 16
+    // (dice 0, 0: roll). Global lane g plays position g % n_pos in every episode;
+    // strat_stride > 0: a rolled first roll is the stratified one (start_game,
+    // bgx_engine.h)
+    const uint32_t* start_tab;
+    int n_pos;
+    uint32_t strat_stride;
 };
 
 // Match mode (bgx_match.hip): the two sides of every game are played by two
@@ -312,6 +321,9 @@ hipError_t bgx_launch_pack(const uint8_t* boards, const uint8_t* player, int n, 
                            hipStream_t stream);
 hipError_t bgx_launch_unpack(const uint32_t* packed, int n, uint8_t* out, hipStream_t stream);
 hipError_t bgx_launch_engine_reset(const bgx::EngineDev* e, hipStream_t stream);
+// rollout tally (bgx_rollout.hip): counts[header lane % n_pos][8] += the headers' results
+hipError_t bgx_launch_rollout_tally(const uint32_t* headers, int n_headers, const uint8_t* start_player, int n_pos,
+                                    uint32_t max_episode, unsigned long long* counts, hipStream_t stream);
 hipError_t bgx_launch_topk(const bgx::EngineDev* e, hipStream_t stream);
 hipError_t bgx_launch_select(const bgx::EngineDev* e, hipStream_t stream);   // select + env step
 hipError_t bgx_launch_top5(const float* V, const int32_t* job_off, const int32_t* job_cnt, int n_jobs,
