@@ -439,7 +439,8 @@ int bgx_ipc_close(void* d_ptr, uint64_t offset);
 /* The 2-ply reply expansion alone (the engine's and bgx_two_ply's reply
  * launch, two_ply.py:114-133 before the value calls): for each of n candidate
  * boards, the opponent's legal afterstates for all 21 DICE_ROLLS
- * (two_ply.py:10-32), as packed boards (flag = the opponent) in d_out[cap][8];
+ * (two_ply.py:10-32), as packed boards (flag = the opponent; word 7 = the row's
+ * root slot, job / 21) in d_out[cap][8];
  * job i * 21 + r's records are rows d_off[j] .. d_off[j] + d_cnt[j] - 1
  * (other rows are unused). Parity hook for the board-major reply kernel
  * (BGX_REPLY_BM=0 selects the per-(board, roll) kernel); BGX_E_CAPACITY when

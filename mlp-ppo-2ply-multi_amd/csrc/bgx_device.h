@@ -6,7 +6,7 @@
 //   w[6]     bar1 | bar2 << 4 | off1 << 8 | off2 << 12 | flag << 16
 //            (flag = the player whose indicator features 196/197 are set;
 //             immutable_board.py:122-127)
-//   w[7]     reserved (0)
+//   w[7]     0, except in an IN_TWOPLY launch's output rows: the row's root slot (job / 21)
 // Counts are 0..15 (15 checkers per side), so a nibble is exact.
 //
 // Movegen "node" representation (relative to a wave-uniform root):

@@ -1,6 +1,6 @@
 // bgx_frag.h — host side of the split-fp16 MLP: W1 / b1 -> the MFMA A
 // fragments the MLP kernels keep in LDS (scheme: bgx_mlp.hip header). Used by
-// bgx_set_weights (bgx_abi.cpp) and the host emulation tests (tests/cpuwave/).
+// bgx_set_weights (bgx_abi.cpp net_upload) and the host emulation tests (tests/cpuwave/).
 #pragma once
 #include <cmath>
 #include <cstdint>
