@@ -94,7 +94,17 @@ int bgx_encode_packed(const uint32_t* d_packed, int n, float* d_out, int layout,
 typedef struct bgx_net bgx_net;
 
 /* BackgammonPolicyNetwork (agents/policy_network.py:36-70) weights, host fp32:
- * h_W1 [128][198] (fc1.weight), h_b1 [128], h_w2 [128] (value_head.weight), h_b2 [1]. */
+ * h_W1 [128][198] (fc1.weight), h_b1 [128], h_w2 [128] (value_head.weight), h_b2 [1].
+ *
+ * Weight limit (every entry point that takes weights: bgx_net_create,
+ * bgx_set_weights, bgx_engine_set_opponent): every entry of the four tensors
+ * must be finite, and max|log2(e) w| over h_W1 (columns 193 / 195, the
+ * borne-off features, divided by 15) and h_b1 must stay below 2^26, i.e.
+ * |w| < 4.65e7: the MFMA path stores W1 / b1 as two fp16 terms under one
+ * power-of-two scale whose exponent is clamped, and at 2^26 the scaled weight
+ * leaves fp16. Anything else is BGX_E_ARG, with the offending tensor named in
+ * bgx_last_error, before any device write: a rejected bgx_set_weights /
+ * bgx_engine_set_opponent leaves the engine's previous network in force. */
 int bgx_net_create(const float* h_W1, const float* h_b1, const float* h_w2, const float* h_b2,
                    bgx_net** out);
 int bgx_net_destroy(bgx_net* net);

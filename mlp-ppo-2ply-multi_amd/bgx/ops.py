@@ -157,7 +157,9 @@ def _fp(a):
 
 
 class Net:
-    """Device copy of BackgammonPolicyNetwork weights (fp32 + split-fp16 MFMA fragments)."""
+    """Device copy of BackgammonPolicyNetwork weights (fp32 + split-fp16 MFMA fragments).
+    Raises BgxError (BGX_E_ARG) for a non-finite weight or max|log2(e) w| >= 2^26
+    over W1 / b1 (include/bgx.h, bgx_net_create)."""
 
     def __init__(self, weights):
         W1, b1, w2, b2 = weights_from(weights)

@@ -33,8 +33,18 @@ using bgx_frag::build_fragments;
 using bgx_frag::NFRAG;
 
 int net_upload(bgx_net* n, const float* W1, const float* b1, const float* w2, const float* b2) {
+    // the scheme's input limit (include/bgx.h), before anything of `n` changes:
+    // a rejected upload leaves the previous network in force
+    bool nonfinite = false;
+    int at = 0;
+    if (const char* bad = bgx_frag::unrepresentable(W1, b1, w2, b2, &nonfinite, &at)) {
+        if (nonfinite) return fail(BGX_E_ARG, "weights: %s[%d] is not finite", bad, at);
+        return fail(BGX_E_ARG, "weights: %s[%d] = %g: max|log2(e) w| must stay below 2^26 (split-fp16 scaling limit)",
+                    bad, at, (double)(bad[0] == 'W' ? W1 : b1)[at]);
+    }
     std::vector<uint16_t> frag;
     const int e = build_fragments(W1, b1, frag);
+    if (e == bgx_frag::kBadWeights) return fail(BGX_E_ARG, "weights: W1 / b1 outside the split-fp16 scaling limit");
     n->feat_scale = (float)std::ldexp(1.0, -e);
     HIP_TRY(hipMemcpy(n->W1, W1, 128 * 198 * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(n->b1, b1, 128 * 4, hipMemcpyHostToDevice));

@@ -14,6 +14,8 @@
 // normal range carry absolute errors ~2^-25 / 2^e, negligible. W = W_hi + W_lo,
 // both fp16; the MFMA multiplies are exact and accumulate in fp32, so two
 // passes give ~fp32 accuracy (|dV| < 1e-5 on the trained checkpoint).
+// e is clamped to [-11, 13]; the host rejects max|-log2(e) w| >= 2^26, where the
+// e = -11 clamp would overflow fp16, and non-finite weights (bgx_frag.h, net_upload).
 //
 // Features for k-steps 0..11 come from a 256-entry LDS table: one byte of the
 // packed board = the counts of two adjacent point slots -> their 8 fp16

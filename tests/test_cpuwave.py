@@ -250,6 +250,162 @@ def test_mlp_kernels_emulated_equal_oracle_value(tmp_path):
         assert np.abs(v - ref).max() < 1e-6, (nt, np.abs(v - ref).max())
 
 
+@pytest.fixture(scope="module")
+def mlp_emu(tmp_path_factory):
+    """mlp_emu built once for the weight-range tests below (AddressSanitizer on)."""
+    tmp = tmp_path_factory.mktemp("mlp_emu")
+    src = _emu_sources(tmp)
+    exe = tmp / "mlp_emu"
+    subprocess.run([CLANG, "-std=c++20", "-O1", "-g", "-w", "-fsanitize=address", "-fno-omit-frame-pointer",
+                    "-I" + str(src), "-I" + os.path.join(HERE, "cpuwave"), "-I" + os.path.join(REPO, "include"),
+                    "-x", "c++", os.path.join(HERE, "cpuwave", "mlp_emu.cpp"), "-o", str(exe), "-pthread"],
+                   check=True, capture_output=True, text=True)
+    return exe
+
+
+# the weight sets of tests/value_cases.py the emulated kernels run (the scaling
+# exponent e from 8 down to the -11 clamp, the mx == 0 branch, a bias-set e,
+# exact 0 / 1 sigmoids); the GPU tests (test_gpu_value_range.py) run all of them
+EMU_SETS = ["ckpt_x2^6", "ckpt_x2^14", "clamp_lo", "zero_hidden", "bias_dominates", "saturated", "one_big"]
+
+
+def _range_check(name, w, v, boards, players, orc, what):
+    """The tolerance rule of value_cases.tolerance on one emulated run."""
+    import value_cases as vc
+    x = orc.encode_many(boards, players)
+    v64 = orc.value(w, x)
+    tol, e32 = vc.tolerance(name, vc.value_f32(w, x), v64)
+    if name in vc.CLOSED_FORM:
+        v64 = np.full(len(v64), vc.closed_form(name, w))
+    assert v.shape == v64.shape and np.isfinite(v).all(), (name, what)
+    err = float(np.abs(v - v64).max())
+    print(f"{name} {what}: err {err:.3g} fp32 {e32:.3g} bound {tol:.3g}")
+    assert err <= tol, (name, what, err, e32, tol)
+
+
+@pytest.mark.skipif(not os.path.exists(CLANG), reason="no ROCm clang")
+@pytest.mark.parametrize("name", EMU_SETS)
+def test_mlp_kernels_emulated_across_weight_ranges(tmp_path, mlp_emu, name):
+    """test_mlp_kernels_emulated_equal_oracle_value off the shipped weights:
+    both kernels of the launcher on 96 LUT-edge boards (counts up to 15 in
+    either nibble of a packed byte, bars and borne-off up to 15) plus 64 random
+    placements, under weight sets whose scaling exponent e differs from the two
+    the shipped sets reach. V is finite and within max(1e-5, 4 x the error of a
+    plain fp32 forward) of the oracle's fp64 value (1e-6 where V has a closed
+    form): the split-fp16 product stays at fp32's own accuracy at every e."""
+    orc = pytest.importorskip("oracle")
+    import value_cases as vc
+    from test_gpu_parity import _random_positions
+    eb, ep = vc.edge_sample(96)
+    pos = _random_positions(5, 64)
+    boards = np.concatenate([eb, np.stack([p[0] for p in pos])])
+    pl = np.concatenate([ep, np.array([p[1] for p in pos], np.uint8)])
+    _pack(boards, pl).tofile(tmp_path / "rows.bin")
+    w = vc.weight_sets()[name]
+    vc.write_weights(w, tmp_path / "w.bin")
+    env = {**os.environ, "ASAN_OPTIONS": "verify_asan_link_order=0:detect_leaks=0"}
+    for nt in ("1", "2"):
+        out = tmp_path / ("v" + nt + ".bin")
+        r = subprocess.run([str(mlp_emu), str(tmp_path / "rows.bin"), str(tmp_path / "w.bin"), nt, str(out)],
+                           capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        _range_check(name, w, np.fromfile(out, np.float32), boards, pl, orc, "nt=" + nt)
+
+
+@pytest.mark.skipif(not os.path.exists(CLANG), reason="no ROCm clang")
+@pytest.mark.parametrize("name", EMU_SETS)
+def test_mlp_delta_kernel_emulated_across_weight_ranges(tmp_path, mlp_emu, name):
+    """The reply MLP by difference (mlp_kernel_delta) under the same weight
+    sets: the replies to 8 random positions and 4 LUT-edge boards for all 21
+    rolls, by the same tolerance rule. The root accumulators are -h log2(e)
+    whatever e is; the difference term carries the 2^-e feature scale."""
+    orc = pytest.importorskip("oracle")
+    import value_cases as vc
+    from test_gpu_parity import _random_positions
+    eb, ep = vc.edge_sample(96)
+    pos = _random_positions(9, 8) + [(eb[i], int(ep[i])) for i in (5, 30, 60, 90)]
+    rolls = [(a, b) for a in range(1, 7) for b in range(a, 7)]
+    roots, reps, slot, opp = [], [], [], []
+    for i, (board, mover) in enumerate(pos):
+        o = 1 - int(mover)
+        roots.append(_pack(board[None], np.array([mover]))[0])
+        for a, b in rolls:
+            n, res, _ = orc.movegen(board, o, a, b)
+            reps += list(res[:n])
+            slot += [i] * n
+            opp += [o] * n
+    reps = np.stack(reps)
+    opp = np.array(opp, np.uint8)
+    rows = _pack(reps, opp)
+    rows[:, 7] = np.array(slot, np.uint32)
+    rows.tofile(tmp_path / "rows.bin")
+    np.stack(roots).astype(np.uint32).tofile(tmp_path / "roots.bin")
+    w = vc.weight_sets()[name]
+    vc.write_weights(w, tmp_path / "w.bin")
+    env = {**os.environ, "ASAN_OPTIONS": "verify_asan_link_order=0:detect_leaks=0"}
+    out = tmp_path / "vd.bin"
+    r = subprocess.run([str(mlp_emu), str(tmp_path / "rows.bin"), str(tmp_path / "w.bin"), "d", str(out),
+                        str(tmp_path / "roots.bin")], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert len(reps) > 1000
+    _range_check(name, w, np.fromfile(out, np.float32), reps, opp, orc, "delta")
+
+
+@pytest.mark.skipif(not os.path.exists(CLANG), reason="no ROCm clang")
+def test_build_fragments_host_check(tmp_path):
+    """bgx_frag.h on the host under AddressSanitizer and UBSan
+    (tests/cpuwave/frag_check.cpp), one w.bin per weight set of
+    tests/value_cases.py: the returned e is the intended one, every fragment
+    half is finite, (hi + lo) 2^-e reproduces -log2(e) w to 2^-25 2^-e absolute
+    or 2^-21 relative, and each fragment index maps back to its (row, k).
+    Weights the scheme cannot represent (a NaN or an inf in any tensor,
+    max|log2(e) w| >= 2^26) are rejected with the tensor named, and
+    build_fragments builds nothing from them."""
+    import value_cases as vc
+    exe = tmp_path / "frag_check"
+    subprocess.run([CLANG, "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined,float-cast-overflow",
+                    "-fno-sanitize-recover=all",
+                    "-fno-omit-frame-pointer", "-I" + os.path.join(REPO, "mlp-ppo-2ply-multi_amd", "csrc"),
+                    os.path.join(HERE, "cpuwave", "frag_check.cpp"), "-o", str(exe)],
+                   check=True, capture_output=True, text=True)
+    env = {**os.environ, "ASAN_OPTIONS": "verify_asan_link_order=0:detect_leaks=0"}
+    sets = vc.weight_sets()
+
+    def run(w, expect):
+        vc.write_weights(w, tmp_path / "w.bin")
+        return subprocess.run([str(exe), str(tmp_path / "w.bin"), expect], capture_output=True, text=True,
+                              timeout=120, env=env)
+
+    for name, w in sets.items():
+        r = run(w, str(vc.INTENDED_E[name]))
+        assert r.returncode == 0, (name, r.stdout[-2000:], r.stderr[-3000:])
+        assert '"mismatches": 0' in r.stdout and '"nonfinite": 0' in r.stdout and '"unmapped": 0' in r.stdout, name
+    ckpt = sets["ckpt"]
+    bad = []
+    for t, idx in (("W1", (100, 7)), ("b1", (5,)), ("w2", (127,)), ("b2", (0,))):
+        for v in (np.nan, np.inf, -np.inf):
+            w = {k: a.copy() for k, a in ckpt.items()}
+            w[t][idx] = v
+            bad.append((w, t))
+    w = {k: a.copy() for k, a in sets["seed0"].items()}
+    w["W1"][:] = 5e7
+    bad.append((w, "W1"))
+    w = {k: a.copy() for k, a in sets["seed0"].items()}
+    w["b1"][3] = -np.float32(2.0 ** 26)
+    bad.append((w, "b1"))
+    bad.append((vc.scaled(ckpt, 23), "W1"))   # mx in [2^26, 2^27): the first scale the e = -11 clamp cannot hold
+    bad.append((vc.scaled(ckpt, 24), "W1"))   # the silent NaN of the old code (scaled weights past fp16)
+    for w, t in bad:
+        r = run(w, "bad:" + t)
+        assert r.returncode == 0, (t, r.stdout[-2000:], r.stderr[-3000:])
+        assert '"rejected": "%s"' % t in r.stdout
+    # a borne-off column just under the limit after its / 15 is accepted: the limit is on the scaled weight
+    w = {k: a.copy() for k, a in sets["seed0"].items()}
+    w["W1"][9, 193] = 5e7
+    r = run(w, str(14 - int(np.floor(np.log2(vc.scaled_max(w))))))
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+
+
 @pytest.mark.skipif(not os.path.exists(CLANG), reason="no ROCm clang")
 def test_mlp_delta_kernel_emulated_equals_oracle_value(tmp_path):
     """The 2-ply reply MLP by difference from the root (mlp_kernel_delta: the
