@@ -13,8 +13,9 @@
 //      LDS), then its choice items (two lanes per wave, one per half-wave:
 //      softmax(V/T) sample and the env step lane_advance -- apply, rewards,
 //      record, reset -- on the LDS-resident lane state), then step s + 1's
-//      tier-1 movegen jobs (one lane each, in the wave's own LDS slice,
-//      bgx_movegen.h, afterstates into the lane's candidate slots). A choice
+//      tier-1 movegen jobs (one lane each, or two rule-mode non-doubles lanes
+//      in one wave, job_records_pair; in the wave's own LDS slice,
+//      bgx_movegen.h, afterstates into the lanes' candidate slots). A choice
 //      waits for the tiles holding its lanes' rows, a job for its lane's
 //      choice (LDS flags); the MFMA-bound tiles, the latency-bound choices and
 //      the issue-bound movegen jobs share the SIMDs.
@@ -62,6 +63,7 @@ template <int FL> struct FusedTail {
     int cnt[FL];                    // lane's full candidate count this step (-1: redo in tier 2)
     int go[2];                      // step s runs iff go[s & 1] (the balanced launch's tickets)
     int qn[2];                      // the step queue's item counters (by pass parity)
+    int ncl;                        // lanes whose next tier-1 job is claimed this step (pipelined queue)
     unsigned tdone[64];             // MLP tile t of this step is written iff tdone[t] == the step's tag
     unsigned chosen[FL];            // lane v of this step is stepped iff chosen[v] == the step's tag
     unsigned claim[FL];             // lane v's next tier-1 job is taken iff claim[v] == the step's tag
@@ -98,6 +100,11 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
     // the cooperative tier 2 at 12 waves only (at 8 waves, 256 registers, its
     // registers spill in the step loop: 0 -> 19)
     constexpr bool COOP2 = NW > 8;
+    // two rule-mode non-doubles jobs per wave (FusedArgs::pair) in the 32-lane
+    // workgroup only: with 16 lanes on 12 waves a step has about one job per
+    // wave, pairing them leaves waves idle, and the code costs the 16-lane
+    // kernel registers (measured slower at 4,096 lanes: DESIGN.md section 9)
+    constexpr bool PAIR = FL == 32;
     constexpr int NT = 64 * NW;          // threads
     extern __shared__ __attribute__((aligned(16))) unsigned long long smem[];
     uint8_t* lds = (uint8_t*)smem;
@@ -145,6 +152,11 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
     unsigned long long tjd[4] = {0, 0, 0, 0};   // tier-1 job clocks / counts: doubles, non-doubles
     unsigned long long tcs[3] = {0, 0, 0};      // choice: state + Philox refill, pick, env step (lane_advance)
     unsigned long long tms[3] = {0, 0, 0};      // MLP tile: rows + k mask, MFMA chain issue, drain + epilogue
+    // pairing: clocks / count of the non-doubles rule-mode two-move jobs run
+    // alone; pipelined claims, those of a rule-mode non-doubles lane, and those
+    // of them that saw a second such lane ready and unclaimed; clocks / count
+    // of the pair items (two jobs each)
+    unsigned long long tpr[7] = {0, 0, 0, 0, 0, 0, 0};
     constexpr bool prof = PROF;
     auto tick = [&](int k) {
         if (prof && t == 0) {
@@ -155,10 +167,17 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
     };
     // ---------------------------------------------------------------- pipelined steps
     // Step s is one LDS item queue: its MLP tiles, then its choice items (a pair
-    // of lanes each), then the next step's tier-1 jobs (one lane each). A choice
-    // item waits (LDS flags, bounded) for the tiles holding its lanes' rows; a
-    // tier-1 job waits for its lane's choice. Every item a waiting item needs
-    // is handed out before it, and tiles wait on nothing, so the waits end.
+    // of lanes each), then the next step's tier-1 jobs (one item per lane). A
+    // choice item waits (LDS flags, bounded) for the tiles holding its lanes'
+    // rows; a tier-1 job item waits for a stepped, unclaimed lane. Every item a
+    // waiting item needs is handed out before it, and tiles wait on nothing, so
+    // the waits end. A job item that claimed a rule-mode non-doubles lane
+    // claims one more such lane when one is ready at that moment (never waiting
+    // for one) and expands both in one pass, so job items can outnumber the
+    // lanes left: claims only grow and T.ncl counts them, every lane's choice
+    // is handed out before any job item, and a job item either claims a lane,
+    // or sees all of the step's lanes claimed and ends as a no-op, or reaches
+    // the poll bound (BGX_ERRF_WAIT_BOUND).
     // The MFMA-bound tiles, the latency-bound choice chains and the issue-bound
     // tier-1 jobs then share the SIMDs instead of running in barrier-separated
     // phases; the barriers left per step are the ones around the workgroup
@@ -319,6 +338,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
             if (t == 0) {
                 T.qn[0] = NW;
                 T.qn[1] = NW;
+                T.ncl = 0;
             }
             ++qtag;
             M1.map[l] = 0u;   // (tier 2 may have used the scratch)
@@ -463,11 +483,13 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                         // lane order behind the choices (a lane's job waits for its
                         // choice), doubles first when the queue holds jobs only
                         const int kj = it - qt - qp;
-                        int v;
+                        int v, v2 = -1;   // the item's lane; the lane paired with it (or none)
                         if (pipelined) {
                             // the first stepped and unclaimed lane, doubles (the long
-                            // jobs) first; every job item claims one lane, and every
-                            // lane's choice was handed out before any job item
+                            // jobs) first. Every lane's choice was handed out before
+                            // any job item and claims only grow (T.ncl counts them), so
+                            // an item either claims a lane, or sees every lane claimed
+                            // (pairs leave items over: a no-op), or reaches the bound.
                             v = -1;
                             for (unsigned spin = 0; v < 0; ++spin) {
                                 const bool ready =
@@ -483,9 +505,15 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                                     if (l == 0) {
                                         const unsigned old = T.claim[cand];
                                         won = old != qtag && atomicCAS(&T.claim[cand], old, qtag) == old;
+                                        if (PAIR && won) atomicAdd(&T.ncl, 1);
                                     }
                                     if (uniform(won)) v = cand;
+                                    if (prof && v >= 0) tpr[2] += 1;
                                 } else {
+                                    // every lane claimed: an item left over by the pairs
+                                    if (PAIR &&
+                                        uniform(__hip_atomic_load(&T.ncl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) >= nj)
+                                        break;
                                     if (spin >= (1u << 24)) {   // bounded
                                         if (l == 0) atomicOr(e.err_flags, BGX_ERRF_WAIT_BOUND);
                                         v = kj;
@@ -497,27 +525,99 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                         } else {
                             v = kj < nd ? select_bit(dmask, kj) : select_bit(omask, kj - nd);
                         }
+                        if (PAIR && pipelined && v >= 0 && (f.pair || prof) && T.st[v].d0 != T.st[v].d1) {
+                            // a rule-mode non-doubles lane (pairable: T.st) takes one more
+                            // such lane, ready and unclaimed now, with the same
+                            // compare-and-swap: two attempts, no waiting
+                            const bool free_l =
+                                act(l) &&
+                                __hip_atomic_load(&T.chosen[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == qtag &&
+                                __hip_atomic_load(&T.claim[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != qtag;
+                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                            const bool cls = (free_l || l == v) && T.st[l].d0 != T.st[l].d1 &&
+                                             nd_by_rule(make_root(T.st[l].w, (int)T.st[l].p));
+                            const uint32_t mc = (uint32_t)ballot(cls);
+                            uint32_t mf = mc & ~(1u << v);
+                            if ((mc >> v) & 1u) {
+                                if (prof) {
+                                    tpr[3] += 1;
+                                    if (mf) tpr[4] += 1;
+                                }
+                                for (int att = 0; att < 2 && mf && v2 < 0 && f.pair; ++att) {
+                                    const int c2 = __ffs(mf) - 1;
+                                    mf &= mf - 1u;
+                                    int won2 = 0;
+                                    if (l == 0) {
+                                        const unsigned old = T.claim[c2];
+                                        won2 = old != qtag && atomicCAS(&T.claim[c2], old, qtag) == old;
+                                        if (won2) atomicAdd(&T.ncl, 1);
+                                    }
+                                    if (uniform(won2)) v2 = c2;
+                                }
+                            }
+                        }
                         const unsigned long long q0 = prof ? wall_clock64() : 0ull;
-                        const LaneState& st = T.st[v];
-                        if (l < 8)
-                            T.job[v][l] = l < 7 ? st.w[l] : (uint32_t)st.p | ((uint32_t)st.d0 << 8) | ((uint32_t)st.d1 << 16);
-                        const JobIn in =
-                            make_job(st.w[0], st.w[1], st.w[2], st.w[3], st.w[4], st.w[5], st.w[6], st.p, st.d0, st.d1);
+                        // the pair in one pass (job_records_pair), else the item's
+                        // lanes one after the other (v < 0: no lane left, no-op)
+                        bool paired = false;
+                        if (PAIR && v2 >= 0) {
+                            // both lanes' job words first: the pair builds its roots from them
+                            if (l < 16) {
+                                const int vq = l < 8 ? v : v2, k = l & 7;
+                                const LaneState& sq = T.st[vq];
+                                T.job[vq][k] =
+                                    k < 7 ? sq.w[k] : (uint32_t)sq.p | ((uint32_t)sq.d0 << 8) | ((uint32_t)sq.d1 << 16);
+                            }
+                            wave_sync();
+                            int na = 0, nb = 0;
+                            paired = f.force_tier < 2 &&
+                                     job_records_pair<false>(a, g * FL + v, T.job[v], g * FL + v2, T.job[v2], M1, na, nb);
+                            wave_sync();
+                            if (paired && l == 0) {
+                                T.cnt[v] = na;
+                                T.cnt[v2] = nb;
+                            }
+                            if (prof && paired) {
+                                tpr[5] += wall_clock64() - q0;
+                                tpr[6] += 1;
+                            }
+                        }
+                        const int nv = !PAIR ? 1 : (v < 0 ? 0 : (v2 >= 0 ? 2 : 1));
+                        for (int q = 0; q < nv; ++q) {
+                            const int vq = q ? v2 : v;
+                            const unsigned long long q1 = prof ? wall_clock64() : 0ull;
+                            const LaneState& st = T.st[vq];
+                            if (l < 8)
+                                T.job[vq][l] =
+                                    l < 7 ? st.w[l] : (uint32_t)st.p | ((uint32_t)st.d0 << 8) | ((uint32_t)st.d1 << 16);
+                            if (paired) continue;
+                            const JobIn in =
+                                make_job(st.w[0], st.w[1], st.w[2], st.w[3], st.w[4], st.w[5], st.w[6], st.p, st.d0, st.d1);
 #if BGX_FUSED_LEAF
-                        // path doubles stream their leaves past the slice's list (no tier 2)
-                        FlatCursor fcj;
-                        const int nf = f.force_tier >= 2 ? -1 : run_job<false, true>(a, g * FL + v, in, M1, fcj);
+                            // path doubles stream their leaves past the slice's list (no tier 2)
+                            FlatCursor fcj;
+                            const int nf = f.force_tier >= 2 ? -1 : run_job<false, true>(a, g * FL + vq, in, M1, fcj);
 #else
-                        uint32_t* fin = nullptr;
-                        const int nf = f.force_tier >= 2 ? -1 : job_records<false>(in, M1, fin, 0x7FFFFFFF);
-                        if (nf >= 0) emit_records<false>(a, g * FL + v, in, fin, nf, 0);
+                            int rule2 = 0;
+                            uint32_t* fin = nullptr;
+                            const int nf = f.force_tier >= 2
+                                               ? -1
+                                               : job_records<false>(in, M1, fin, 0x7FFFFFFF, prof ? &rule2 : nullptr);
+                            if (nf >= 0) emit_records<false>(a, g * FL + vq, in, fin, nf, 0);
 #endif
-                        wave_sync();
-                        if (l == 0) T.cnt[v] = nf;
-                        if (prof) {
-                            const int kd = in.d0 == in.d1 ? 0 : 2;
-                            tjd[kd] += wall_clock64() - q0;
-                            tjd[kd + 1] += 1;
+                            wave_sync();
+                            if (l == 0) T.cnt[vq] = nf;
+                            if (prof) {
+                                const int kd = in.d0 == in.d1 ? 0 : 2;
+                                tjd[kd] += wall_clock64() - q1;
+                                tjd[kd + 1] += 1;
+#if !BGX_FUSED_LEAF
+                                if (rule2) {
+                                    tpr[0] += wall_clock64() - q1;
+                                    tpr[1] += 1;
+                                }
+#endif
+                            }
                         }
                     }
                     int kn = 0;
@@ -670,6 +770,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
             atomicAdd(P + 6, tms[0]);
             atomicAdd(P + 22, tms[1]);
             atomicAdd(P + 23, tms[2]);
+            for (int k = 0; k < 7; ++k) atomicAdd(P + 88 + k, tpr[k]);
         }
     }
     if (t == 0) {

@@ -263,6 +263,7 @@ struct bgx_engine {
     int force_tier = 0;
     bool prof_enabled = false;
     int fused_fl = 0;              // BGX_FUSED_LANES: fused 1-ply lanes per workgroup (16 / 32; 0 = auto)
+    int fused_pair = 1;            // BGX_FUSED_PAIR: two rule-mode non-doubles jobs per wave (0 = off; A/B, tests)
     DevBuf<uint8_t> dice_tab;      // bgx_engine_set_dice
     DevBuf<uint32_t> start_tab;    // bgx_engine_set_start (EngineDev::start_tab)
     // optional hipGraph of the last n_steps sequence

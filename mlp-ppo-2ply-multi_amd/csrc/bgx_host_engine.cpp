@@ -79,6 +79,7 @@ int bgx_engine_create(int device, const bgx_config* cfg, bgx_engine** out) {
         if (const char* v = getenv("BGX_MG_TEST_TIER")) e->force_tier = atoi(v);
         e->prof_enabled = getenv("BGX_FUSED_PROF") != nullptr;
         if (const char* v = getenv("BGX_FUSED_LANES")) e->fused_fl = atoi(v);
+        if (const char* v = getenv("BGX_FUSED_PAIR")) e->fused_pair = atoi(v) != 0;
         e->cfg = *cfg;
         // ring slots: a power of two (slot = record counter & (R - 1) stays exact
         // when the 32-bit counter wraps)

@@ -33,6 +33,22 @@ void fused_prof_report(const unsigned long long* p, int n_slots, FILE* out, cons
             s[11] / (s[12] > 0 ? s[12] : 1) / 100);
     fprintf(out, "[bgx fused prof] tier-1 job: doubles %.2f us (%.0f jobs), non-doubles %.2f us (%.0f jobs)\n",
             s[14] / (s[15] > 0 ? s[15] : 1) / 100, s[15], s[16] / (s[17] > 0 ? s[17] : 1) / 100, s[17]);
+    // pairing: the non-doubles jobs that took the rule-mode two-move branch
+    // alone (words 88 / 89: clocks, count) against all item clocks, how often a
+    // pipelined claim of a rule-mode non-doubles lane saw a second such lane
+    // ready and unclaimed (words 90..92: claims, of such a lane, with a
+    // partner), and the pair items (words 93 / 94: clocks, count; their clocks
+    // are in no other word)
+    const double items = s[8] + s[10] + s[14] + s[16] + s[93];
+    fprintf(out, "[bgx fused prof] tier-1 rule-mode two-move job: %.2f us (%.0f jobs), %.2f wave-us per workgroup "
+            "step, %.1f %% of the item wave-us\n", s[88] / (s[89] > 0 ? s[89] : 1) / 100, s[89], s[88] / n / 100,
+            100.0 * s[88] / (items > 0 ? items : 1));
+    fprintf(out, "[bgx fused prof] pipelined job claims %.0f: %.0f of a rule-mode non-doubles lane, %.0f of them "
+            "(%.1f %%) with a second such lane ready and unclaimed\n", s[90], s[91], s[92],
+            100.0 * s[92] / (s[91] > 0 ? s[91] : 1));
+    fprintf(out, "[bgx fused prof] tier-1 pair items: %.0f pairs formed (%.2f per workgroup step), %.2f us each, "
+            "%.2f wave-us per workgroup step\n", s[94], s[94] / n, s[93] / (s[94] > 0 ? s[94] : 1) / 100,
+            s[93] / n / 100);
     // the last launch, per workgroup: duration spread, dispatch skew, and the
     // rows / tier-2 jobs of the slowest vs the median workgroup
     std::vector<std::pair<double, int>> dur;

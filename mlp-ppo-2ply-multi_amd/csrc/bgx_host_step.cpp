@@ -248,6 +248,7 @@ static int enqueue_fused(bgx_engine* e, int n_steps, hipStream_t s) {
     f.ws_words_per_block = (size_t)5 * e->ws_slots;
     f.force_tier = e->force_tier;
     f.lanes_per_wg = e->fused_fl;
+    f.pair = e->fused_pair;
     if (e->cfg.balance) {   // n_steps x lanes lane-steps; a lane runs at most n + n/4 + 4 (ring headroom)
         f.budget = (long long)n_steps * (long long)e->cfg.lanes;
         const int headroom = e->cfg.ring - e->cfg.max_steps;

@@ -237,6 +237,8 @@ struct FusedArgs {
     unsigned long long* prof;    // development (BGX_FUSED_PROF): [gridDim.x][16] phase clocks, or null
     int lanes_per_wg;            // 16 or 32 game lanes per workgroup; 0: the launcher picks (32 when
                                  //   every CU still gets a workgroup)
+    int pair;                    // BGX_FUSED_PAIR: a pipelined job item expands two rule-mode non-doubles
+                                 //   lanes in one wave (job_records_pair) when a second one is ready
     // balanced launch (bgx_config.balance): each workgroup-step takes a ticket of
     // its lanes from budget_ctr[0] and steps while the running total is below
     // `budget` lane-steps, at most n_cap steps; budget <= 0: every lane runs

@@ -773,8 +773,10 @@ BGX_DEV bool expand_keep(const Mem& M, const Moves& pm, int c, KeyFn kfn, uint32
 // returns the record count, or -1 when the slice overflowed (fallback)
 // heavy_t: a doubles level with more children than this returns -2 (the
 // small-launch kernel then expands the job with the whole block)
+// rule2 (or null; the fused development report): set to 1 when the job took
+// the non-doubles rule-mode two-move branch
 template <bool G>
-BGX_DEV int job_records(const JobIn& in, const Mem& M, uint32_t*& fin_out, int heavy_t) {
+BGX_DEV int job_records(const JobIn& in, const Mem& M, uint32_t*& fin_out, int heavy_t, int* rule2 = nullptr) {
     STAMP_BEGIN;
     const Root& R = in.R;
     const int l = lane_id();
@@ -830,6 +832,7 @@ BGX_DEV int job_records(const JobIn& in, const Mem& M, uint32_t*& fin_out, int h
         if ((two1 || (nH != 1 && two2)) && rule) {
             STAMP(1);
             STAMP_COUNT(4);
+            if (rule2) *rule2 = 1;
             // 2-move records without a table (nd_first): a pass-2 parent can
             // only add its chain (s2 = t1) or reverse chain (s2 -> s1) child
             if (pass == 1) {
@@ -1041,6 +1044,129 @@ BGX_DEV void emit_records(const MovegenArgs& a, int j, const JobIn& in, const ui
             emit_one(a, j, in.R, n, i, base);
         }
     }
+}
+
+// a lane's own root from a job's 8 words (packed board words 0..6, then
+// player | d0 << 8 | d1 << 16): make_job's root on the VALU, no scalar copy
+BGX_DEV Root root_of_words(const uint32_t* q, int& d0, int& d1) {
+    const uint32_t w0 = q[0], w1 = q[1], w2 = q[2], w3 = q[3], w4 = q[4], w5 = q[5], w6 = q[6], pd = q[7];
+    const bool p2 = (pd & 255u) != 0u;
+    d0 = (int)((pd >> 8) & 255u);
+    d1 = (int)(pd >> 16);
+    Root R;
+    R.m0 = p2 ? w3 : w0; R.m1 = p2 ? w4 : w1; R.m2 = p2 ? w5 : w2;
+    R.o0 = p2 ? w0 : w3; R.o1 = p2 ? w1 : w4; R.o2 = p2 ? w2 : w5;
+    const uint32_t b0 = w6 & 15u, b1 = (w6 >> 4) & 15u, f0 = (w6 >> 8) & 15u, f1 = (w6 >> 12) & 15u;
+    R.bar = p2 ? b1 : b0; R.obar = p2 ? b0 : b1;
+    R.off = p2 ? f1 : f0; R.ooff = p2 ? f0 : f1;
+    R.block = ge2_24(R.o0, R.o1, R.o2);
+    R.blot = occ24(R.o0, R.o1, R.o2) & ~R.block;
+    R.player = p2 ? 1 : 0;
+    return R;
+}
+
+// Two non-doubles rule-mode jobs A and B (nd_by_rule, no force_table) in one
+// wave, as job_records' rule branch + emit_records of each alone. qa / qb are
+// the jobs' 8 words in the wave's memory space (board words 0..6, then
+// player | d0 << 8 | d1 << 16). A's first moves of both passes sit in lanes
+// 0..31 (pass = (l >> 4) & 1, k = l & 15), B's in lanes 32..63; the job of a
+// lane or a parent lane p is p >> 5. The two roots are per-half vector
+// values: each lane builds its own job's root from the words (the root
+// analysis runs once, on the VALU, for both; no scalar copy of either job),
+// and a child gets its parent's job values (player, dice, block, blot,
+// occupancy) by shuffle with the parent's move. The flat child order is A's
+// children, then B's, so the kept list holds A's keys (nA of them, today's
+// order) followed by B's; one emit pass writes every entry to its own job's
+// slots, record indices restarting at 0 for B, the k >= cap cut per job
+// (emit_one). Returns false, with nothing written, when either job has no
+// two-move play (job_records' test) or the combined list would not fit the
+// slice's list under expand_keep's 64-entry margin: the caller then runs the
+// jobs one after the other. The parent map is zero on entry and on return.
+template <bool G>
+BGX_DEV bool job_records_pair(const MovegenArgs& a, int jA, const uint32_t* qa, int jB, const uint32_t* qb,
+                              const Mem& M, int& nA, int& nB) {
+    const int l = lane_id();
+    const bool hb = l >= 32;
+    int d0, d1;
+    const Root R = root_of_words(hb ? qb : qa, d0, d1);
+    const int H = d0 > d1 ? d0 : d1, L = d0 > d1 ? d1 : d0;
+    // rule mode: the root is not on the bar and not bearing off, so its move
+    // list for a die is its occupancy with an open destination (node_moves)
+    const uint32_t occ0 = occ24(R.m0, R.m1, R.m2);
+    const uint32_t okH = ok_mask(R.block, H, R.player), okL = ok_mask(R.block, L, R.player);
+    const int pass = (l >> 4) & 1, k = l & 15;
+    const int dA = pass ? L : H;
+    const uint32_t src1 = occ0 & (pass ? okL : okH);
+    const bool v1 = k < __popc(src1);
+    int s1 = 0;
+    if (v1) s1 = select_bit_fast(src1, k);
+    const uint32_t t1 = (uint32_t)dest_of(R, s1, dA);
+    const uint32_t last1 = nib(R.m0, R.m1, R.m2, s1) == 1u ? 1u << s1 : 0u;
+    uint32_t src2 = ((occ0 & ~last1) | (1u << (t1 & 31u))) & (pass ? okH : okL);
+    const uint64_t cm = ballot(v1 && src2 != 0u);       // parents with a second move
+    const uint64_t h1m = ballot(__popc(occ0 & okH) == 1);   // nH == 1 (the same in every lane of a half)
+    const bool twoA = (cm & 0xFFFFull) != 0ull || (!(h1m & 1ull) && (cm & 0xFFFF0000ull) != 0ull);
+    const bool twoB = ((cm >> 32) & 0xFFFFull) != 0ull || (!((h1m >> 32) & 1ull) && (cm >> 48) != 0ull);
+    if (!twoA || !twoB) return false;
+    const bool h1 = v1 && t1 < 24u && ((R.blot >> t1) & 1u);
+    // a pass-2 parent can only add its chain (s2 = t1) or reverse chain (s2 -> s1) child
+    if (pass == 1) {
+        const int rv = R.player == 0 ? s1 - H : s1 + H;
+        src2 &= (t1 < 24u ? 1u << t1 : 0u) | ((rv >= 0 && rv < 24) ? 1u << rv : 0u);
+    }
+    const int cc = v1 ? __popc(src2) : 0;
+    const uint32_t blot2 = R.blot & ~(h1 ? (1u << t1) : 0u);
+    // what a child needs of its parent beside the move lists, in three words
+    const uint32_t meta = (uint32_t)s1 | (t1 << 5) | ((uint32_t)h1 << 10) | ((uint32_t)R.player << 11) |
+                          ((uint32_t)H << 12) | ((uint32_t)L << 15);
+    uint32_t* const fin = M.pa ? M.pa : M.fa;
+    const int cap = M.pa ? M.PF : M.F;
+    int nfin = 0;
+    nA = 0;
+    const int incl = wave_incl_scan(cc);
+    const int excl = incl - cc;
+    const int T = lane63(incl);
+    for (int b = 0; b < T; b += 64) {
+        const int r = b + l;
+        const int p = flat_parent<G>(M.map, excl, cc, b);
+        const int j = r - __shfl(excl, p, 64);
+        const int s2 = select_bit_fast((uint32_t)__shfl((int)src2, p, 64), j);
+        const uint32_t pm = (uint32_t)__shfl((int)meta, p, 64);
+        const uint32_t pb2 = (uint32_t)__shfl((int)blot2, p, 64);
+        const uint32_t pocc = (uint32_t)__shfl((int)occ0, p, 64);
+        Root Rp{};   // the parent's job: what dest_of and nd_first read
+        Rp.player = (int)((pm >> 11) & 1u);
+        Rp.block = (uint32_t)__shfl((int)R.block, p, 64);
+        Rp.blot = (uint32_t)__shfl((int)R.blot, p, 64);
+        const int ps1 = (int)(pm & 31u), pt1 = (int)((pm >> 5) & 31u);
+        const bool ph1 = ((pm >> 10) & 1u) != 0u;
+        const int pH = (int)((pm >> 12) & 7u), pL = (int)((pm >> 15) & 7u);
+        const int pp = (p >> 4) & 1;
+        const int t2 = dest_of(Rp, s2, pp ? pH : pL);
+        const bool h2 = ((pb2 >> t2) & 1u) != 0u;
+        const uint32_t key = nd_first(Rp, pocc, pp, ps1, pt1, s2, t2, pH, pL)
+                                 ? nd_key((uint32_t)ps1, (uint32_t)pt1, ph1, (uint32_t)s2, (uint32_t)t2, h2)
+                                 : ND_DROP;
+        const bool sv = r < T && key != ND_DROP;
+        const uint64_t bm = ballot(sv);
+        if (nfin + 64 > cap) return false;
+        if (sv) st32<G>(fin + nfin + mask_prefix(bm), key);
+        nfin += __popcll(bm);
+        nA += __popcll(ballot(sv && p < 32));
+    }
+    sync<G>();
+    nB = nfin - nA;
+    for (int b = 0; b < nfin; b += 64) {
+        const int i = b + l;
+        if (i < nfin) {
+            const uint32_t e = ld32<G>(fin + i);
+            const bool eb = i >= nA;
+            int e0, e1;
+            const Root Re = root_of_words(eb ? qb : qa, e0, e1);
+            emit_one(a, eb ? jB : jA, Re, nd_board(Re, e), eb ? i - nA : i, 0);
+        }
+    }
+    return true;
 }
 
 // A doubles job by path (doubles_by_path) as job_records + emit_records, except
