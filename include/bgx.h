@@ -391,7 +391,7 @@ int bgx_get_timing(bgx_engine* e, double* ms_movegen, int* n_movegen, double* ms
  * gamma * V[t+1] detached, MSE, backward, clip_grad_norm_(clip), Adam step)
  * with one launch over n_eps episodes of bgx_harvest records (episode e =
  * records [d_offs[e], d_offs[e+1]), at most 2048 each). d_params / d_adam_m /
- * d_adam_v: 25,729 fp32 each in state_dict order (fc1.weight [128][198],
+ * d_adam_v: 25,601 fp32 each in state_dict order (fc1.weight [128][198],
  * fc1.bias, value_head.weight, value_head.bias), updated in place; *d_step =
  * Adam's step count (incremented per episode); d_metrics[5] (double) +=
  * per-episode loss, post-clip grad norm, mean |TD error|, mean V, reward sum.
@@ -399,6 +399,38 @@ int bgx_get_timing(bgx_engine* e, double* ms_movegen, int* n_movegen, double* ms
 int bgx_td0_update(const uint32_t* d_records, const int32_t* d_offs, int n_eps, float* d_params,
                    float* d_adam_m, float* d_adam_v, int* d_step, float lr, float gamma, float grad_clip,
                    double* d_metrics, void* stream);
+
+/* The batched TD(0) update (DeviceTrainer batched=True; a flagged change of the
+ * reference's semantics): ONE Adam step per call on the mean of the
+ * per-episode losses, loss = (1/E) sum_e (1/T_e) sum_s (Y_s - tgt_s)^2 with
+ * bgx_td0_update's targets (no bootstrap across an episode boundary), spread
+ * over all CUs (csrc/bgx_train_batch.hip: f32-input MFMA forward and backward
+ * over 128-record tiles, per-workgroup partial gradients summed in a fixed
+ * order, then clip_grad_norm_(clip) and Adam). Episodes of any length >= 1;
+ * d_offs values are clamped to [0, n_records] on the device. *d_step grows by
+ * 1; d_metrics[5] (double) += E loss, E post-clip grad norm, sum over episodes
+ * of mean |TD error| and of mean V, reward sum, so metrics / E reads like
+ * bgx_td0_update's. d_grad_out: NULL, or [25601] for the pre-clip gradient
+ * (state_dict order). d_work: 16-byte aligned device workspace of at least
+ * bgx_td0_batch_workspace(n_records) bytes, free for reuse once the call's
+ * stream work is done; its first n_records floats then hold V of every
+ * record. The same inputs and state give the same bits on every
+ * call. Asynchronous on `stream`: no host synchronisation and no allocation
+ * (capturable in a stream graph).
+ * BGX_E_ARG: a null required pointer, n_eps <= 0, n_records < n_eps,
+ * work_bytes too small, d_work misaligned. */
+int bgx_td0_update_batched(const uint32_t* d_records, const int32_t* d_offs, int n_eps, int n_records,
+                           float* d_params, float* d_adam_m, float* d_adam_v, int* d_step,
+                           float lr, float gamma, float grad_clip, double* d_metrics,
+                           float* d_grad_out /* NULL, or [25601]: the pre-clip gradient, state_dict order */,
+                           void* d_work, uint64_t work_bytes, void* stream);
+/* bytes of device workspace bgx_td0_update_batched needs for n_records records
+ * (Y + one partial gradient per workgroup, sized for the largest grid the
+ * library launches); pure host arithmetic, no device needed */
+int bgx_td0_batch_workspace(int n_records, uint64_t* bytes);
+/* the backward launch's records per tile and its largest grid (workgroup g
+ * takes tiles g, g + grid, ...; the grid is min(grid, tiles)) */
+int bgx_td0_batch_shape(int* tile, int* grid);
 
 /* Copy-engine transfer helpers (bgx/hostgather.py: the episode gather of
  * the ranks of one node through host shared memory, replacing the pickled

@@ -15,9 +15,13 @@ reference's signature. backend="hip" (the default for records) runs the whole
 update as one libbgx launch (bgx_td0_update, csrc/bgx_train.hip: weights in
 registers, Adam moments in place, no host sync per episode); backend="torch"
 runs it as eager torch ops (observations re-encoded with bgx_encode), the
-checker the HIP path is tested against. batched=True (torch only) is a
-flagged semantic change: one Adam step per update on the mean of the
-per-episode losses.
+checker the HIP path is tested against. batched=True is a flagged semantic
+change: one Adam step per update on the mean of the per-episode losses. It
+runs as eager torch ops unless backend="hip" is asked for explicitly, which
+runs update_records as bgx_td0_update_batched (csrc/bgx_train_batch.hip: the
+forward and backward passes over all CUs, episodes of any length);
+bgx/train_ref.py restates that update in numpy. The three paths share the
+flat state, so a trainer may change backend between updates.
 """
 from __future__ import annotations
 
@@ -38,7 +42,7 @@ MIN_EPISODES_TO_TRAIN = 200   # configuration.py:7
 class DeviceTrainer:
     def __init__(self, parameter_manager, device=None, lr=LEARNING_RATE, gamma=GAMMA,
                  grad_clip=GRAD_CLIP_THRESHOLD, batch_episode_size=MIN_EPISODES_TO_TRAIN, batched=False,
-                 backend="hip"):
+                 backend=None):
         self.parameter_manager = parameter_manager
         self.device = torch.device(device) if device is not None else torch.device("cuda")
         self.policy_network = BackgammonPolicyNetwork().to(self.device)
@@ -49,11 +53,23 @@ class DeviceTrainer:
         self.grad_clip = grad_clip
         self.batch_episode_size = batch_episode_size
         self.batched = batched
+        if backend is None:   # not chosen: the sequential update on HIP, the batched one on torch
+            backend = "torch" if batched else "hip"
         if backend not in ("hip", "torch"):
             raise ValueError(f"backend must be 'hip' or 'torch', not {backend!r}")
-        self.backend = "torch" if batched else backend
+        self.backend = backend
         self.total_episodes = 0
         self._flat = None   # HIP backend state: params / Adam m / v (flat, state_dict order), step
+        self._work = None   # batched HIP backend: the workspace tensor, regrown on demand
+
+    @staticmethod
+    def batch_shape():
+        """(records per tile, largest grid) of the batched HIP backward launch."""
+        import ctypes
+        from ._lib import check, lib
+        tile, grid = ctypes.c_int(0), ctypes.c_int(0)
+        check(lib().bgx_td0_batch_shape(ctypes.byref(tile), ctypes.byref(grid)), "bgx_td0_batch_shape")
+        return tile.value, grid.value
 
     # ------------------------------------------------------------ inputs
     def _from_records(self, headers, records):
@@ -91,7 +107,7 @@ class DeviceTrainer:
         """The same update from compact records (headers [n, 16], records [m, 12],
         each episode's records contiguous in header order); any n >= 1."""
         if self.backend == "hip":
-            return self._update_hip(headers, records)
+            return self._update_hip_batched(headers, records) if self.batched else self._update_hip(headers, records)
         return self._update(*self._from_records(headers, records))
 
     # ------------------------------------------------------------ HIP backend
@@ -175,6 +191,48 @@ class DeviceTrainer:
                                        float(self.gamma), clip, ptr(metrics),
                                        stream_handle(torch.cuda.current_stream(self.device))),
                   "bgx_td0_update")
+        return self._finish_hip(metrics, hdr, lens)
+
+    def _update_hip_batched(self, headers, records):
+        """One bgx_td0_update_batched call: one Adam step on the mean of the
+        per-episode losses (the torch batched path's semantics)."""
+        import ctypes
+        from ._lib import check, lib, ptr, stream_handle
+        rec = torch.as_tensor(records).to(self.device)
+        if rec.dtype != torch.int32:
+            rec = rec.view(torch.int32) if rec.dtype == torch.uint32 else rec.to(torch.int32)
+        rec = rec.contiguous()
+        hdr = np.asarray(torch.as_tensor(headers).cpu().numpy()).astype(np.uint32)
+        lens = hdr[:, 3].astype(np.int64)
+        n_eps, n_rec = len(lens), int(rec.shape[0])
+        if n_eps < 1:
+            raise ValueError("bgx_td0_update_batched: no episodes")
+        if int(lens.min()) <= 0:
+            raise ValueError("bgx_td0_update_batched: an episode has no records")
+        offs_h = np.concatenate([[0], np.cumsum(lens)])
+        if (np.diff(offs_h) < 1).any() or int(offs_h[-1]) != n_rec or n_rec >= 2 ** 31:
+            raise ValueError(f"bgx_td0_update_batched: the headers count {int(offs_h[-1])} records, got {n_rec}")
+        offs = torch.as_tensor(offs_h.astype(np.int32), device=self.device)
+        f = self._hip_state()
+        need = ctypes.c_uint64(0)
+        check(lib().bgx_td0_batch_workspace(n_rec, ctypes.byref(need)), "bgx_td0_batch_workspace")
+        if self._work is None or self._work.numel() < need.value or self._work.device != f["p"].device:
+            self._work = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        metrics = torch.zeros(5, dtype=torch.float64, device=self.device)
+        clip = float(self.grad_clip) if self.grad_clip is not None else 0.0
+        with torch.cuda.device(self.device):   # the trainer's device and its current stream
+            check(lib().bgx_td0_update_batched(ptr(rec), ptr(offs), n_eps, n_rec, ptr(f["p"]), ptr(f["m"]),
+                                               ptr(f["v"]), ptr(f["step"]),
+                                               float(self.optimizer.param_groups[0]["lr"]), float(self.gamma), clip,
+                                               ptr(metrics), None, ptr(self._work), self._work.numel(),
+                                               stream_handle(torch.cuda.current_stream(self.device))),
+                  "bgx_td0_update_batched")
+        return self._finish_hip(metrics, hdr, lens)
+
+    def _finish_hip(self, metrics, hdr, lens):
+        """After a HIP update: the module / optimizer follow the flat state, the
+        weights go to the parameter manager, the device metrics become the dict."""
+        n_eps = len(lens)
         self.total_episodes += n_eps
         self._sync_module()
         a = metrics.tolist()
@@ -206,17 +264,29 @@ class DeviceTrainer:
         # metrics accumulate on the device; one host read per update
         acc = torch.zeros(6, dtype=torch.float64, device=self.device)
         if self.batched:
-            losses = []
+            losses, ys, tgts = [], [], []
             for e in range(n_eps):
                 y, tgt = self._episode_terms(obs, rewards, offs[e], offs[e + 1])
                 losses.append(F.mse_loss(y, tgt))
+                ys.append(y.detach().reshape(-1))
+                tgts.append(tgt.reshape(-1))
             opt.zero_grad()
             loss = torch.stack(losses).mean()
             loss.backward()
-            if self.grad_clip is not None:
-                torch.nn.utils.clip_grad_norm_(params, self.grad_clip)
+            if self.grad_clip is not None and self.grad_clip > 0:   # <= 0: no clipping, as the HIP backend reads it
+                pre = torch.nn.utils.clip_grad_norm_(params, self.grad_clip)
+                post = pre * torch.clamp(self.grad_clip / (pre + 1e-6), max=1.0)
+            else:
+                post = torch.norm(torch.stack([p.grad.detach().norm(2) for p in params if p.grad is not None]), 2)
             opt.step()
+            # the sequential path's metrics, summed over the episodes (the one norm counts for each)
+            yd, tg = torch.cat(ys).double(), torch.cat(tgts).double()
+            inv_t = 1.0 / torch.as_tensor(np.repeat(lens, lens), device=self.device).double()
             acc[0] = loss.detach() * n_eps
+            acc[1] = post.double() * n_eps
+            acc[2] = ((tg - yd).abs() * inv_t).sum()
+            acc[3] = (yd * inv_t).sum()
+            acc[4] = rewards[:offs[-1]].sum().double()
         else:
             for e in range(n_eps):
                 y, tgt = self._episode_terms(obs, rewards, offs[e], offs[e + 1])

@@ -328,6 +328,65 @@ int bgx_td0_update(const uint32_t* d_records, const int32_t* d_offs, int n_eps, 
     });
 }
 
+int bgx_td0_batch_workspace(int n_records, uint64_t* bytes) {
+    return guarded("bgx_td0_batch_workspace", [&]() -> int {
+        if (n_records <= 0 || !bytes) return fail(BGX_E_ARG, "bgx_td0_batch_workspace: n_records=%d", n_records);
+        *bytes = bgx::train_batch_layout(n_records).bytes;
+        return BGX_OK;
+    });
+}
+
+int bgx_td0_batch_shape(int* tile, int* grid) {
+    return guarded("bgx_td0_batch_shape", [&]() -> int {
+        if (!tile || !grid) return fail(BGX_E_ARG, "bgx_td0_batch_shape: null pointer");
+        *tile = bgx::TRAIN_BATCH_TILE;
+        *grid = bgx::TRAIN_BATCH_GRID;
+        return BGX_OK;
+    });
+}
+
+int bgx_td0_update_batched(const uint32_t* d_records, const int32_t* d_offs, int n_eps, int n_records,
+                           float* d_params, float* d_adam_m, float* d_adam_v, int* d_step, float lr, float gamma,
+                           float grad_clip, double* d_metrics, float* d_grad_out, void* d_work, uint64_t work_bytes,
+                           void* stream) {
+    return guarded("bgx_td0_update_batched", [&]() -> int {
+        if (n_eps <= 0 || n_records < n_eps)
+            return fail(BGX_E_ARG, "bgx_td0_update_batched: n_eps=%d n_records=%d", n_eps, n_records);
+        if (!d_records || !d_offs || !d_params || !d_adam_m || !d_adam_v || !d_step || !d_metrics || !d_work)
+            return fail(BGX_E_ARG, "bgx_td0_update_batched: null pointer");
+        const bgx::TrainBatchLayout l = bgx::train_batch_layout(n_records);
+        if (work_bytes < l.bytes)
+            return fail(BGX_E_ARG, "bgx_td0_update_batched: work_bytes=%llu < %llu (bgx_td0_batch_workspace)",
+                        (unsigned long long)work_bytes, (unsigned long long)l.bytes);
+        if ((uintptr_t)d_work % 16 != 0) return fail(BGX_E_ARG, "bgx_td0_update_batched: d_work is not 16-byte aligned");
+        DeviceScope ds(d_params);   // the kernels run on the device holding the parameters
+        HIP_TRY(ds.err);
+        char* w = (char*)d_work;
+        bgx::TrainBatchArgs a{};
+        a.rec = d_records;
+        a.offs = d_offs;
+        a.n_eps = n_eps;
+        a.n_rec = n_records;
+        a.params = d_params;
+        a.adam_m = d_adam_m;
+        a.adam_v = d_adam_v;
+        a.step = d_step;
+        a.lr = lr;
+        a.gamma = gamma;
+        a.grad_clip = grad_clip;
+        a.metrics = d_metrics;
+        a.grad_out = d_grad_out;
+        a.Y = (float*)(w + l.Y);
+        a.info = (int32_t*)(w + l.info);
+        a.partial = (float*)(w + l.partial);
+        a.grad = (float*)(w + l.grad);
+        a.mpart = (double*)(w + l.mpart);
+        a.sqpart = (double*)(w + l.sqpart);
+        HIP_TRY(bgx_launch_td0_batched(&a, (hipStream_t)stream));
+        return BGX_OK;
+    });
+}
+
 int bgx_reply_moves(const uint8_t* d_boards, const uint8_t* d_opponent, int n, uint32_t* d_out, int cap,
                     int32_t* d_off, int32_t* d_cnt, void* stream) {
     return guarded("bgx_reply_moves", [&]() -> int {

@@ -295,6 +295,52 @@ struct TrainArgs {
     double* metrics;             // [5] += loss, post-clip grad norm, |td| mean, V mean, reward sum (per episode)
 };
 
+// Batched TD(0) update (bgx_train_batch.hip): one Adam step per call on the mean
+// of the per-episode losses, over all CUs. The workspace (TrainBatchLayout) holds
+// Y and the episode info of every record, one partial gradient per workgroup of
+// the largest grid, the summed gradient and the launches' partial sums.
+constexpr int TRAIN_BATCH_TILE = 128;        // records per backward tile
+constexpr int TRAIN_BATCH_GRID = 256;        // most workgroups a forward / backward launch has
+constexpr int TRAIN_BATCH_PARAMS = 25601;    // 128 * 198 + 128 + 128 + 1
+constexpr int TRAIN_BATCH_PSTRIDE = 25604;   // floats per partial-gradient row (16-byte rows)
+constexpr int TRAIN_BATCH_SQ = 128;          // slots for the reduce launch's sums of squares
+struct TrainBatchArgs {
+    const uint32_t* rec;         // [n_rec][12]
+    const int32_t* offs;         // [n_eps + 1], clamped to [0, n_rec] on the device
+    int n_eps, n_rec;
+    float* params;               // TrainArgs layout, 25,601 floats each
+    float* adam_m;
+    float* adam_v;
+    int* step;
+    float lr, gamma, grad_clip;  // grad_clip <= 0: no clipping
+    double* metrics;             // [5] += E loss, E post-clip norm, sum_e mean |td|, sum_e mean V, reward sum
+    float* grad_out;             // null, or [25601]: the pre-clip gradient
+    // workspace
+    float* Y;                    // [n_rec] V of every record
+    int32_t* info;               // [n_rec] the record's episode length | (last record of it) << 31; 0: in no episode
+    float* partial;              // [TRAIN_BATCH_GRID][TRAIN_BATCH_PSTRIDE]
+    float* grad;                 // [TRAIN_BATCH_PSTRIDE]
+    double* mpart;               // [TRAIN_BATCH_GRID][4] metric shares per workgroup
+    double* sqpart;              // [TRAIN_BATCH_SQ]
+    int n_tiles, grid;           // set by the launcher
+};
+// byte offsets of the workspace's parts (each 16-byte aligned) and its size
+struct TrainBatchLayout {
+    uint64_t Y, info, partial, grad, mpart, sqpart, bytes;
+};
+inline TrainBatchLayout train_batch_layout(int n_rec) {
+    const uint64_t n4 = ((uint64_t)n_rec + 3) / 4 * 4;
+    TrainBatchLayout l{};
+    l.Y = 0;
+    l.info = l.Y + 4 * n4;
+    l.partial = l.info + 4 * n4;
+    l.grad = l.partial + (uint64_t)TRAIN_BATCH_GRID * TRAIN_BATCH_PSTRIDE * 4;
+    l.mpart = l.grad + (uint64_t)TRAIN_BATCH_PSTRIDE * 4;
+    l.sqpart = l.mpart + (uint64_t)TRAIN_BATCH_GRID * 4 * 8;
+    l.bytes = l.sqpart + (uint64_t)TRAIN_BATCH_SQ * 8;
+    return l;
+}
+
 // the 2-ply top-5 launch: at most this many waves (2,048 blocks of 4), each
 // with its own record-count slot (bgx_launch_top5's rec_acc)
 constexpr int T5_WAVES = 2048 * 4;
@@ -335,6 +381,7 @@ hipError_t bgx_launch_top5(const float* V, const int32_t* job_off, const int32_t
                                                                      // (bgx::T5_WAVES slots, or null)
 hipError_t bgx_launch_two_ply_reduce(const float* job_val, int n, double* out, hipStream_t stream);
 hipError_t bgx_launch_td0(const bgx::TrainArgs* args, hipStream_t stream);
+hipError_t bgx_launch_td0_batched(const bgx::TrainBatchArgs* args, hipStream_t stream);
 // harvest: episode offsets / totals (info[4] on the device, hinfo[4] host-mapped
 // or null), then the headers + records gather (persistent grid; the episode
 // count is read on the device)

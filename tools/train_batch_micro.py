@@ -1,0 +1,142 @@
+#!/usr/bin/env python3
+"""Batched-trainer micro-benchmark (tools only): one harvest of self-play
+episodes (repeated to reach the larger sizes), then per size
+
+  batched_hip   one bgx_td0_update_batched call, event-timed on the stream
+  sequential    one bgx_td0_update call on the same records, event-timed
+  batched_torch DeviceTrainer(batched=True, backend="torch").update_records,
+                wall clock around a synchronize (an eager path: its host work
+                is the path)
+
+as the median of --reps runs after a warm-up. Prints one JSON line with
+episodes/s and records/s of each and the batched call's TFLOP/s, counting
+3 x 2 x 198 x 128 FLOP per record (forward, recomputed forward, dW1) against
+the 157.3 TF f32-MFMA peak. --only hip runs the batched call alone (for a
+kernel trace, which gives the launches' shares)."""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(REPO, "mlp-ppo-2ply-multi_amd"), os.path.join(REPO, "tools")]
+from bgx import Engine  # noqa: E402
+from bgx._lib import check, lib, ptr, stream_handle  # noqa: E402
+from bgx.net import BackgammonPolicyNetwork  # noqa: E402
+from bgx.ops import weights_from  # noqa: E402
+from bgx.trainer import DeviceTrainer  # noqa: E402
+from train_loop import LocalPM  # noqa: E402
+
+FLOP_PER_RECORD = 3 * 2 * 198 * 128
+PEAK_TF = 157.3
+
+
+def harvest(n_eps):
+    """headers (host) and records (device) of n_eps episodes: one harvest, repeated as needed."""
+    pm = LocalPM(BackgammonPolicyNetwork().state_dict())
+    eng = Engine(lanes=4096, seed=0)
+    eng.set_weights(dict(zip(("W1", "b1", "w2", "b2"), weights_from(pm.get_parameters()))), 1.5, 1)
+    eng.step(300)
+    h = eng.harvest()
+    hdr, rec = h.headers.cpu(), h.records.clone()
+    eng.close()
+    k = min(n_eps, hdr.shape[0])
+    hdr = hdr[:k]
+    rec = rec[:int(hdr[:, 3].sum())]
+    reps = -(-n_eps // k)
+    hdr = hdr.repeat(reps, 1)[:n_eps].clone()
+    rec = rec.repeat(reps, 1)[:int(hdr[:, 3].sum())].contiguous()
+    return pm, hdr, rec
+
+
+def event_ms(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return statistics.median(out)
+
+
+def flat_state(pm, dev):
+    sd = pm.get_parameters()
+    p = torch.cat([sd[k].reshape(-1) for k in DeviceTrainer._KEYS]).float().to(dev).contiguous()
+    return p, torch.zeros_like(p), torch.zeros_like(p), torch.zeros(1, dtype=torch.int32, device=dev)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", type=int, nargs="+", default=[200, 2000, 20000])
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--only", choices=("hip",), default=None)
+    ap.add_argument("--torch-max-reps", type=int, default=5)
+    args = ap.parse_args()
+    dev = torch.device("cuda")
+    torch.manual_seed(0)
+    pm, hdr_all, rec_all = harvest(max(args.sizes))
+    L = lib()
+    out = []
+    for n_eps in args.sizes:
+        hdr = hdr_all[:n_eps]
+        lens = hdr[:, 3].numpy().astype(np.int64)
+        n_rec = int(lens.sum())
+        rec = rec_all[:n_rec].contiguous()
+        offs = torch.as_tensor(np.concatenate([[0], np.cumsum(lens)]).astype(np.int32), device=dev)
+        row = {"episodes": n_eps, "records": n_rec}
+        # ---- the batched HIP call
+        p, m, v, step = flat_state(pm, dev)
+        need = ctypes.c_uint64(0)
+        check(L.bgx_td0_batch_workspace(n_rec, ctypes.byref(need)))
+        work = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        met = torch.zeros(5, dtype=torch.float64, device=dev)
+        s = stream_handle()
+
+        def batched():
+            check(L.bgx_td0_update_batched(ptr(rec), ptr(offs), n_eps, n_rec, ptr(p), ptr(m), ptr(v), ptr(step),
+                                           1e-3, 0.99, 1.0, ptr(met), None, ptr(work), need.value, s))
+
+        ms = event_ms(batched, args.reps)
+        row["batched_hip"] = {"ms": ms, "episodes_per_s": n_eps / ms * 1e3, "records_per_s": n_rec / ms * 1e3,
+                              "tflops": n_rec * FLOP_PER_RECORD / ms * 1e-9,
+                              "of_f32_mfma_peak": n_rec * FLOP_PER_RECORD / ms * 1e-9 / PEAK_TF}
+        if args.only is None:
+            # ---- the sequential kernel (one Adam step per episode)
+            p, m, v, step = flat_state(pm, dev)
+
+            def sequential():
+                check(L.bgx_td0_update(ptr(rec), ptr(offs), n_eps, ptr(p), ptr(m), ptr(v), ptr(step), 1e-3, 0.99,
+                                       1.0, ptr(met), s))
+
+            ms = event_ms(sequential, min(args.reps, 5))
+            row["sequential"] = {"ms": ms, "episodes_per_s": n_eps / ms * 1e3, "records_per_s": n_rec / ms * 1e3}
+            # ---- the eager torch batched path
+            tr = DeviceTrainer(pm, device="cuda", batch_episode_size=n_eps, batched=True, backend="torch")
+            reps = min(args.torch_max_reps, args.reps) if n_eps <= 2000 else 2
+            tr.update_records(hdr, rec)
+            torch.cuda.synchronize()
+            ts = []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                tr.update_records(hdr, rec)
+                torch.cuda.synchronize()
+                ts.append((time.perf_counter() - t0) * 1e3)
+            ms = statistics.median(ts)
+            row["batched_torch"] = {"ms": ms, "runs": reps, "episodes_per_s": n_eps / ms * 1e3,
+                                    "records_per_s": n_rec / ms * 1e3}
+        out.append(row)
+    print(json.dumps({"sizes": out}))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Self-play + training on one GPU without Python Episode objects (SURVEY §8f
 rows 1-3 together): the engine plays, every finished episode's compact
-records feed DeviceTrainer.update_records in the reference's batches of 200,
+records feed DeviceTrainer.update_records in the reference's batches of 200
+(--episodes-per-update N for others; --batched --backend hip for the multi-CU update),
 and each update's weights go straight back into the engine with the
 reference temperature schedule (ParameterManager.get_temperature)."""
 import argparse
@@ -44,11 +45,15 @@ def main():
     ap.add_argument("--lanes", type=int, default=4096)
     ap.add_argument("--updates", type=int, default=20)
     ap.add_argument("--batched", action="store_true")
-    ap.add_argument("--backend", default="hip", choices=("hip", "torch"))
+    ap.add_argument("--backend", default=None, choices=("hip", "torch"),
+                    help="unset: hip for the sequential update, torch for --batched (DeviceTrainer's rule)")
+    ap.add_argument("--episodes-per-update", type=int, default=200, metavar="N",
+                    help="episodes per trainer update (the reference's batch is 200)")
     args = ap.parse_args()
+    per = args.episodes_per_update
     torch.manual_seed(0)
     pm = LocalPM(BackgammonPolicyNetwork().state_dict())
-    trainer = DeviceTrainer(pm, device="cuda", batched=args.batched, backend=args.backend)
+    trainer = DeviceTrainer(pm, device="cuda", batch_episode_size=per, batched=args.batched, backend=args.backend)
     eng = Engine(lanes=args.lanes, seed=0)
     w = dict(zip(("W1", "b1", "w2", "b2"), weights_from(pm.get_parameters())))
     eng.set_weights(w, pm.get_temperature(), pm.version)
@@ -62,24 +67,24 @@ def main():
             hdr_buf.append(h.headers.cpu())
             rec_buf.append(h.records)
         n = sum(x.shape[0] for x in hdr_buf)
-        while n >= 200 and done < args.updates:
+        while n >= per and done < args.updates:
             hdr, rec = torch.cat(hdr_buf), torch.cat(rec_buf)
-            k = int(hdr[:200, 3].sum())
+            k = int(hdr[:per, 3].sum())
             t1 = time.perf_counter()
-            m = trainer.update_records(hdr[:200], rec[:k])
+            m = trainer.update_records(hdr[:per], rec[:k])
             torch.cuda.synchronize()
             t_train += time.perf_counter() - t1
-            hdr_buf, rec_buf = [hdr[200:]], [rec[k:]]
-            n -= 200
+            hdr_buf, rec_buf = [hdr[per:]], [rec[k:]]
+            n -= per
             done += 1
             w = dict(zip(("W1", "b1", "w2", "b2"), weights_from(pm.get_parameters())))
             eng.set_weights(w, pm.get_temperature(), pm.version)
     el = time.perf_counter() - t0
-    print(json.dumps({"updates": done, "episodes_trained": 200 * done, "env_steps": steps * args.lanes,
+    print(json.dumps({"updates": done, "episodes_trained": per * done, "env_steps": steps * args.lanes,
                       "wall_s": el, "train_s": t_train, "updates_per_s": done / el,
-                      "train_episodes_per_s": 200 * done / t_train, "last_loss": m["loss"],
+                      "train_episodes_per_s": per * done / t_train, "train_share": t_train / el, "last_loss": m["loss"],
                       "version": pm.version, "temperature": pm.get_temperature(), "batched": args.batched,
-                      "backend": trainer.backend}))
+                      "backend": trainer.backend, "episodes_per_update": per}))
 
 
 if __name__ == "__main__":
