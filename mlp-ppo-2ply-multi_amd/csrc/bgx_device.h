@@ -274,7 +274,19 @@ BGX_DEV Node apply_move(const Root& r, Node n, int s, int d) {
 }
 
 // ------------------------------------------------------------ wave helpers
+#ifdef BGX_LANE_ID_AT_USE
+// the lane id recomputed at each use (two VALU instructions): opaque to the
+// compiler, so a lane predicate (lane_id() < 13 ...) is a compare where it is
+// used and not a mask hoisted in front of the caller's outermost loop and held
+// in an SGPR pair from there (bgx_fused.hip, at its register cap, defines this)
+BGX_DEV int lane_id() {
+    int l = (int)__lane_id();
+    asm volatile("" : "+v"(l));
+    return l & 63;
+}
+#else
 BGX_DEV int lane_id() { return (int)__lane_id(); }
+#endif
 BGX_DEV uint64_t ballot(bool p) { return __ballot(p); }
 // number of set lanes below this lane in mask
 BGX_DEV int mask_prefix(uint64_t m) {

@@ -26,6 +26,9 @@
 // (bgx_abi.cpp enqueue_steps: movegen, mlp, select_step) does; the lanes of a
 // workgroup wait only for each other, never for the other 8,000 lanes, and
 // there is no per-step launch.
+// lane_id() is opaque in this unit (bgx_device.h): at the kernel's register cap
+// every lane predicate hoisted in front of the step loop is a spilled SGPR pair
+#define BGX_LANE_ID_AT_USE 1
 #include "bgx_engine.h"
 #include "bgx_mlp.h"
 #include "bgx_movegen.h"
@@ -91,8 +94,40 @@ template <int FL> struct FCfg {
     static_assert(XS >= 24 && LDS <= 160 * 1024, "fits the CU's LDS");
 };
 
+// This launch's arguments, read where they are used. The kernel never touches
+// its by-value parameter: a value loaded from it in the prologue stays live
+// across the persistent step loop, and at the register cap that is a spilled
+// SGPR (a v_writelane once, a v_readlane + s_nop at every use; 109 of the 289
+// SGPR spills were these pointers and sizes). Each call gives the kernarg
+// segment's address (the FusedArgs sit at offset 0) as a wave-uniform value
+// the compiler cannot see through, so the loads behind it are scalar loads
+// from constant memory (the scalar data cache serves them) that can be neither
+// hoisted above the call nor shared with another call's: one call at the head
+// of each queue item, and the item's fields are live in that item only. Reads
+// only; every store stays a vector store.
+__device__ __forceinline__ const FusedArgs& launch_args() {
+    auto p = __builtin_amdgcn_kernarg_segment_ptr();   // constant address space
+    asm volatile("" : "+s"(p));
+    return *(const FusedArgs*)p;
+}
+// the movegen's view of them (slot output into the lanes' candidate rows)
+__device__ __forceinline__ MovegenArgs job_args(const FusedArgs& f) {
+    MovegenArgs a{};
+    a.out_mode = OUT_PACKED_SLOT;
+    a.cap = f.cap;
+    a.out_packed = f.cand;
+    a.out_count = const_cast<int32_t*>(f.e.cand_cnt);
+    a.ws_global = f.ws_global;
+    a.ws_slots = f.ws_slots;
+    a.ws_words_per_wave = f.ws_words_per_block;
+    a.heavy_t = 0x7FFFFFFF;
+    a.force_tier = f.force_tier;
+    a.err_flags = f.e.err_flags;
+    return a;
+}
+
 template <bool PROF, int FL>
-__global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_kernel(FusedArgs f) {
+__global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_kernel(FusedArgs) {
     using C = FCfg<FL>;
     constexpr int NW = C::NW, SL1 = C::SL1, F_W = C::F_W, F_TAIL = C::F_TAIL, XS = C::XS;
     constexpr int P1_S = C::P1_S, P1_F = C::P1_F, P1_PF = C::P1_PF;
@@ -110,10 +145,12 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
     uint8_t* lds = (uint8_t*)smem;
     FusedTail<FL>& T = *(FusedTail<FL>*)(lds + F_TAIL);
     float* xs = (float*)(lds + F_TAIL + sizeof(FusedTail<FL>));   // [FL][XS] lane values
-    const EngineDev& e = f.e;
     const int t = (int)threadIdx.x, w = t >> 6, l = lane_id();
-    for (int i = t; i < 256; i += NT) T.lut[i] = lut_entry((uint32_t)i, f.feat_scale);
-    for (int i = t; i < 128; i += NT) T.w2s[i] = f.rowc[i];
+    {
+        const FusedArgs& f = launch_args();
+        for (int i = t; i < 256; i += NT) T.lut[i] = lut_entry((uint32_t)i, f.feat_scale);
+        for (int i = t; i < 128; i += NT) T.w2s[i] = f.rowc[i];
+    }
     for (int i = t; i < 64; i += NT) T.tdone[i] = 0u;
     for (int i = t; i < FL; i += NT) T.chosen[i] = T.claim[i] = 0u;
     unsigned qtag = 0u;   // this workgroup's step counter (tags the flags; never 0 on a live step)
@@ -122,22 +159,13 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
     // of a wave in flight at once; the prologue's lane loads overlap them)
     uint4* wl = (uint4*)(lds + F_W);
     static_assert(NFRAG % 64 == 0, "W fragments in whole wave chunks");
-    for (int c = w; c < NFRAG / 64; c += NW)
-        __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)(void*)(f.wfrag + 64 * c + l),
-                                         (__attribute__((address_space(3))) void*)(void*)(wl + 64 * c), 16, 0, 0);
+    {
+        const uint4* const wsrc = launch_args().wfrag;
+        for (int c = w; c < NFRAG / 64; c += NW)
+            __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)(void*)(wsrc + 64 * c + l),
+                                             (__attribute__((address_space(3))) void*)(void*)(wl + 64 * c), 16, 0, 0);
+    }
     const uint4* wf = wl;
-
-    MovegenArgs a{};
-    a.out_mode = OUT_PACKED_SLOT;
-    a.cap = f.cap;
-    a.out_packed = f.cand;
-    a.out_count = const_cast<int32_t*>(e.cand_cnt);
-    a.ws_global = f.ws_global;
-    a.ws_slots = f.ws_slots;
-    a.ws_words_per_wave = f.ws_words_per_block;
-    a.heavy_t = 0x7FFFFFFF;
-    a.force_tier = f.force_tier;
-    a.err_flags = e.err_flags;
 
     unsigned long long n_rows = 0, n_fb = 0, n_steps = 0;
     const unsigned long long wg_begin = PROF ? wall_clock64() : 0ull;   // this launch's span (f.prof)
@@ -184,7 +212,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
     // tiers (tier 2) and the row prefix. The tiles read their rows from the
     // candidate buffer (L2) rather than from a staged copy in the scratch, which
     // holds the waves' tier-1 slices during the queue.
-    const int groups = (e.L + FL - 1) / FL;
+    const int groups = (launch_args().e.L + FL - 1) / FL;
     uint32_t* const slw = (uint32_t*)(lds + (size_t)w * SL1);   // this wave's tier-1 slice
     Mem M1;
     M1.map = slw;
@@ -198,12 +226,19 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
     M1.PF = P1_PF;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's W fragment loads landed (a barrier follows)
     for (int g = (int)blockIdx.x; g < groups; g += (int)gridDim.x) {
-        const int nlive = e.L - g * FL < FL ? e.L - g * FL : FL;
-        for (int v = t; v < nlive; v += NT) {
-            lane_load(e, g * FL + v, T.st[v]);
-            if (f.t1_ready) T.cnt[v] = f.t1cnt[g * FL + v];   // the previous launch expanded these positions
+        int nlive, n_iter;
+        bool t1_ready;
+        {
+            const FusedArgs& f = launch_args();
+            nlive = f.e.L - g * FL < FL ? f.e.L - g * FL : FL;
+            n_iter = f.budget > 0 ? f.n_cap : f.n_steps;
+            t1_ready = f.t1_ready != 0;
+            for (int v = t; v < nlive; v += NT) {
+                lane_load(f.e, g * FL + v, T.st[v]);
+                if (t1_ready) T.cnt[v] = f.t1cnt[g * FL + v];   // the previous launch expanded these positions
+            }
         }
-        if (f.t1_ready) {   // the jobs' words for tier 2 (T.job), from the lane states
+        if (t1_ready) {   // the jobs' words for tier 2 (T.job), from the lane states
             __syncthreads();
             for (int q = t; q < nlive * 8; q += NT) {
                 const int v = q >> 3, k = q & 7;
@@ -225,6 +260,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
         // keyed by lane and its counter), so which lanes step when changes nothing
         // but how far each lane has got at a harvest.
         auto ticket = [&](int s) -> int {
+            const FusedArgs& f = launch_args();
             const int full = nlive << 8;
             if (f.budget <= 0) return s < f.n_steps ? full : 0;
             if (s >= f.n_cap) return 0;
@@ -246,13 +282,12 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
             for (unsigned spin = 0; __hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != qtag;
                  ++spin) {
                 if (spin >= (1u << 24)) {
-                    if (l == 0) atomicOr(e.err_flags, BGX_ERRF_WAIT_BOUND);
+                    if (l == 0) atomicOr(launch_args().e.err_flags, BGX_ERRF_WAIT_BOUND);
                     break;
                 }
                 __builtin_amdgcn_s_sleep(1);
             }
         };
-        const int n_iter = f.budget > 0 ? f.n_cap : f.n_steps;
         if (prof && t == 0 && !t_loop0) t_loop0 = wall_clock64();
         // step -1 is the first step's tier-1 queue alone; step s >= 0: tier 2 and
         // the row prefix of step s, then its queue (tiles, choice pairs, step
@@ -281,6 +316,8 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                     const uint32_t* q = T.job[v];
                     const JobIn in = make_job(q[0], q[1], q[2], q[3], q[4], q[5], q[6], (int)(q[7] & 255u),
                                               (int)((q[7] >> 8) & 255u), (int)(q[7] >> 16));
+                    const FusedArgs& f = launch_args();   // the redo's workspace, tier hook and output
+                    const MovegenArgs a = job_args(f);
                     FlatCursor fc;
                     auto run_global = [&]() -> int {
                         uint32_t* base = f.ws_global + (size_t)blockIdx.x * f.ws_words_per_block;
@@ -296,7 +333,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                         sync<true>();
                         if (prof) ++t3n;
                         const int r = run_job<true>(a, j, in, G, fc);
-                        if (r < 0 && l == 0) atomicOr(e.err_flags, BGX_ERRF_FALLBACK_OVERFLOW);
+                        if (r < 0 && l == 0) atomicOr(a.err_flags, BGX_ERRF_FALLBACK_OVERFLOW);
                         return r < 0 ? 0 : r;
                     };
                     int r2 = -1;
@@ -325,7 +362,8 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                 // ---- 2. row prefix (lanes that pass evaluate nothing), every wave
                 // computes it (identical values)
                 const int c = act(l) ? T.cnt[l] : 0;   // lanes outside this step's range: no rows
-                const int rows = l < FL && c > 0 ? 1 + (c < f.cap ? c : f.cap) : 0;
+                const int cap = launch_args().cap;
+                const int rows = l < FL && c > 0 ? 1 + (c < cap ? c : cap) : 0;
                 const int incl = wave_incl_scan(rows);
                 if (l <= FL) T.pre[l] = incl - rows;
                 wave_sync();
@@ -347,7 +385,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
             // step s + 1's tier-1 jobs (every step: the last one's results are
             // the next launch's first; at step -1, unless the previous launch
             // left them)
-            const int nj = step >= 0 || !f.t1_ready ? hi - lo : 0;
+            const int nj = step >= 0 || !t1_ready ? hi - lo : 0;
             // the next step's jobs, doubles first, when nothing runs beside them
             const bool dbl = act(l) && T.st[l].d0 == T.st[l].d1;
             const uint32_t dmask = (uint32_t)ballot(dbl), omask = (uint32_t)ballot(act(l) && !dbl);
@@ -377,6 +415,13 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                         // ---- 3. one MLP tile: its 32 rows from the lanes' obs rows /
                         // candidate slots (L2), all four m-tiles in the wave (mlp_tile4)
                         const unsigned long long i0 = prof ? wall_clock64() : 0ull;
+                        // the tile's constants: under lane_of's LDS reads
+                        const FusedArgs& f = launch_args();
+                        const uint32_t* const k_rows = f.e.rows;
+                        const uint32_t* const k_cand = f.cand;
+                        float* const k_vbuf = f.vbuf;
+                        const int k_cap = f.cap;
+                        const float k_b2 = f.b2, k_fs = f.feat_scale;
                         const int r = it * 32 + (l & 31);
                         uint4 bx = make_uint4(0, 0, 0, 0), by = make_uint4(0, 0, 0, 0);
                         int vl = 0, k = 0;
@@ -385,7 +430,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                             k = r - T.pre[vl];
                             const int li = g * FL + vl;
                             const uint32_t* src =
-                                k == 0 ? e.rows + (size_t)li * 8 : f.cand + ((size_t)li * f.cap + (k - 1)) * 8;
+                                k == 0 ? k_rows + (size_t)li * 8 : k_cand + ((size_t)li * k_cap + (k - 1)) * 8;
                             bx = ((const uint4*)src)[0];
                             by = ((const uint4*)src)[1];
                         }
@@ -396,7 +441,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                             i1 = wall_clock64();
                             tms[0] += i1 - i0;   // rows loaded, lane_of, k mask
                         }
-                        const float v = mlp_tile4<PROF>(wf, T.lut, T.w2s, f.feat_scale, bx, by, km, &i2);
+                        const float v = mlp_tile4<PROF>(wf, T.lut, T.w2s, k_fs, bx, by, km, &i2);
                         if (prof) {
                             const float vv = __shfl(v, 0);   // the epilogue's value is ready
                             asm volatile("" ::"v"(vv));
@@ -405,9 +450,9 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                             tms[2] += i3 - i2;   // drain + epilogue
                         }
                         if (l < 32 && r < nr) {
-                            const float val = v + f.b2;
+                            const float val = v + k_b2;
                             if (k < XS) xs[vl * XS + k] = val;
-                            else f.vbuf[(size_t)(g * FL + vl) * (f.cap + 1) + k] = val;
+                            else k_vbuf[(size_t)(g * FL + vl) * (k_cap + 1) + k] = val;
                         }
                         // the tile's values (LDS and, past XS, vbuf) before its flag
                         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -416,6 +461,9 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                     } else if (it < qt + qp) {
                         // ---- 4. action choice + env step of two lanes, one per half-wave
                         const int p = it - qt;
+                        // the choice's constants: under the flag waits
+                        const FusedArgs& f = launch_args();
+                        const EngineDev& e = f.e;
                         if (pipelined) {
                             const int va = lo + 2 * p, vb = lo + 2 * p + 2 < hi ? lo + 2 * p + 2 : hi;
                             const int r0 = T.pre[va], r1 = T.pre[vb];   // the pair's rows [r0, r1)
@@ -483,6 +531,10 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                         // lane order behind the choices (a lane's job waits for its
                         // choice), doubles first when the queue holds jobs only
                         const int kj = it - qt - qp;
+                        // the job's constants: under the claim loop
+                        const FusedArgs& f = launch_args();
+                        const MovegenArgs a = job_args(f);
+                        const bool k_pair = f.pair != 0;
                         int v, v2 = -1;   // the item's lane; the lane paired with it (or none)
                         if (pipelined) {
                             // the first stepped and unclaimed lane, doubles (the long
@@ -515,7 +567,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                                         uniform(__hip_atomic_load(&T.ncl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) >= nj)
                                         break;
                                     if (spin >= (1u << 24)) {   // bounded
-                                        if (l == 0) atomicOr(e.err_flags, BGX_ERRF_WAIT_BOUND);
+                                        if (l == 0) atomicOr(a.err_flags, BGX_ERRF_WAIT_BOUND);
                                         v = kj;
                                         break;
                                     }
@@ -525,7 +577,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                         } else {
                             v = kj < nd ? select_bit(dmask, kj) : select_bit(omask, kj - nd);
                         }
-                        if (PAIR && pipelined && v >= 0 && (f.pair || prof) && T.st[v].d0 != T.st[v].d1) {
+                        if (PAIR && pipelined && v >= 0 && (k_pair || prof) && T.st[v].d0 != T.st[v].d1) {
                             // a rule-mode non-doubles lane (pairable: T.st) takes one more
                             // such lane, ready and unclaimed now, with the same
                             // compare-and-swap: two attempts, no waiting
@@ -543,7 +595,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                                     tpr[3] += 1;
                                     if (mf) tpr[4] += 1;
                                 }
-                                for (int att = 0; att < 2 && mf && v2 < 0 && f.pair; ++att) {
+                                for (int att = 0; att < 2 && mf && v2 < 0 && k_pair; ++att) {
                                     const int c2 = __ffs(mf) - 1;
                                     mf &= mf - 1u;
                                     int won2 = 0;
@@ -570,7 +622,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                             }
                             wave_sync();
                             int na = 0, nb = 0;
-                            paired = f.force_tier < 2 &&
+                            paired = a.force_tier < 2 &&
                                      job_records_pair<false>(a, g * FL + v, T.job[v], g * FL + v2, T.job[v2], M1, na, nb);
                             wave_sync();
                             if (paired && l == 0) {
@@ -596,11 +648,11 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
 #if BGX_FUSED_LEAF
                             // path doubles stream their leaves past the slice's list (no tier 2)
                             FlatCursor fcj;
-                            const int nf = f.force_tier >= 2 ? -1 : run_job<false, true>(a, g * FL + vq, in, M1, fcj);
+                            const int nf = a.force_tier >= 2 ? -1 : run_job<false, true>(a, g * FL + vq, in, M1, fcj);
 #else
                             int rule2 = 0;
                             uint32_t* fin = nullptr;
-                            const int nf = f.force_tier >= 2
+                            const int nf = a.force_tier >= 2
                                                ? -1
                                                : job_records<false>(in, M1, fin, 0x7FFFFFFF, prof ? &rule2 : nullptr);
                             if (nf >= 0) emit_records<false>(a, g * FL + vq, in, fin, nf, 0);
@@ -639,8 +691,9 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                 const unsigned long long c = wall_clock64();
                 if (step >= 0) {
                     if (step_idx < 24) {
-                        atomicAdd(f.prof + (size_t)blockIdx.x * PROF_STRIDE + 32 + step_idx, c - t_step);
-                        atomicAdd(f.prof + (size_t)blockIdx.x * PROF_STRIDE + 64 + step_idx, 1ull);
+                        unsigned long long* const pr = launch_args().prof;
+                        atomicAdd(pr + (size_t)blockIdx.x * PROF_STRIDE + 32 + step_idx, c - t_step);
+                        atomicAdd(pr + (size_t)blockIdx.x * PROF_STRIDE + 64 + step_idx, 1ull);
                     }
                     else { late_sum += c - t_step; ++late_n; }
                     ++step_idx;
@@ -649,6 +702,8 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
             }
         }
         if (prof && t == 0) t_loop1 = wall_clock64();
+        const FusedArgs& f = launch_args();   // the write-back's and the harvest's
+        const EngineDev& e = f.e;
         for (int v = t; v < nlive; v += NT) {
             lane_store(e, g * FL + v, T.st[v]);
             f.t1cnt[g * FL + v] = T.cnt[v];   // the next positions' expansion (f.t1_ready)
@@ -741,6 +796,8 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
         }
         __syncthreads();
     }
+    const FusedArgs& f = launch_args();
+    const EngineDev& e = f.e;
     if (prof) {
         unsigned long long* P = f.prof + (size_t)blockIdx.x * PROF_STRIDE;
         if (t == 0) {
