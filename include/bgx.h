@@ -432,6 +432,38 @@ int bgx_td0_batch_workspace(int n_records, uint64_t* bytes);
  * takes tiles g, g + grid, ...; the grid is min(grid, tiles)) */
 int bgx_td0_batch_shape(int* tile, int* grid);
 
+/* bgx_td0_update_batched with the lambda-return as the target: for an episode
+ * of records a .. b-1 (Y detached),
+ *   G_{b-1} = r_{b-1},
+ *   G_s = r_s + gamma ((1 - lambda) Y_{s+1} + lambda G_{s+1}),  a <= s < b-1,
+ *   loss = (1/E) sum_e (1/T_e) sum_s (Y_s - G_s)^2.
+ * lambda = 0 is TD(0): the call then leaves d_params, the moments, *d_step,
+ * d_metrics, d_grad_out and V in the workspace bit-identical to
+ * bgx_td0_update_batched on the same inputs. lambda = 1 is the discounted
+ * Monte-Carlo return, which does not depend on V. No bootstrap and no carry
+ * across an episode boundary; a record in no episode takes no part. A target
+ * stage between the forward and the backward launch (csrc/bgx_train_lambda.hip:
+ * a wave per episode, a scan over 64-record chunks from the episode's end, one
+ * fixed fma chain per record) computes G on the device; episodes of any length.
+ * The metrics keep their meaning with G as the target (mean |TD error| is mean
+ * |Y - G|). d_target_out: NULL, or [n_records] for G of every record, 0 for a
+ * record in no episode. d_work: 16-byte aligned, at least
+ * bgx_tdlambda_batch_workspace(n_records) bytes (bgx_td0_update_batched's
+ * layout, V first, followed by G). Everything else as bgx_td0_update_batched:
+ * one Adam step, the same bits on every call, asynchronous on `stream`, no host
+ * synchronisation and no allocation (capturable in a stream graph).
+ * BGX_E_ARG: what bgx_td0_update_batched rejects, lambda outside [0, 1] or NaN,
+ * work_bytes below bgx_tdlambda_batch_workspace. */
+int bgx_tdlambda_update_batched(const uint32_t* d_records, const int32_t* d_offs, int n_eps, int n_records,
+                                float* d_params, float* d_adam_m, float* d_adam_v, int* d_step,
+                                float lr, float gamma, float lambda, float grad_clip, double* d_metrics,
+                                float* d_grad_out   /* NULL, or [25601]: the pre-clip gradient, state_dict order */,
+                                float* d_target_out /* NULL, or [n_records]: G of every record */,
+                                void* d_work, uint64_t work_bytes, void* stream);
+/* bytes of device workspace bgx_tdlambda_update_batched needs for n_records
+ * records (bgx_td0_batch_workspace plus G of every record); pure host arithmetic */
+int bgx_tdlambda_batch_workspace(int n_records, uint64_t* bytes);
+
 /* Copy-engine transfer helpers (bgx/hostgather.py: the episode gather of
  * the ranks of one node through host shared memory, replacing the pickled
  * queue of src/main.py:115-133 / multi/experience_queue.py:5-13 without

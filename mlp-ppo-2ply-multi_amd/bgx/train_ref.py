@@ -5,7 +5,8 @@ use. No torch, no GPU, no libbgx.so.
     loss = (1/E) sum_e (1/T_e) sum_s (Y_s - tgt_s)^2,
     tgt_s = r_s + gamma Y_{s+1} (detached; r_s alone on an episode's last record)
 
-batched_td0_reference states the forward pass and the gradient in float64;
+and of its TD(lambda) form (bgx_tdlambda_update_batched), whose target is the
+lambda-return of lambda_returns. batched_td0_reference states the forward pass and the gradient in float64;
 adam_reference states clip_grad_norm_ and the Adam step in float32, in the
 kernel's operation order, which is torch's (sqrt(v) / sqrt(bc2) + eps, then
 p + (-step_size m) / den, every operation correctly rounded).
@@ -49,10 +50,35 @@ def split_params(params):
     return p[:N_W1].reshape(128, 198), p[N_W1:N_W1 + 128], p[N_W1 + 128:N_W1 + 256], p[N_W1 + 256]
 
 
-def batched_td0_reference(params, records, offs, gamma):
+def lambda_returns(Y, rewards, offs, gamma, lam):
+    """The lambda-return of every record, the serial recurrence from each
+    episode's end in the dtype of Y (float64: the checker; float32: the fp32
+    comparison, every operation rounded to float32):
+        G_{b-1} = r_{b-1},  G_s = r_s + gamma ((1 - lam) Y_{s+1} + lam G_{s+1}).
+    A record in no episode keeps 0. lam = 0 is the TD(0) target, lam = 1 the
+    discounted Monte-Carlo return (Y then enters with weight 0)."""
+    Y = np.asarray(Y)
+    dt = Y.dtype.type
+    r = np.asarray(rewards).astype(dt)
+    g, lam = dt(gamma), dt(lam)
+    one_m = dt(1.0) - lam
+    G = np.zeros(len(Y), dt)
+    offs = np.asarray(offs, np.int64)
+    for e in range(len(offs) - 1):
+        a, b = int(offs[e]), int(offs[e + 1])
+        if b <= a:
+            continue
+        G[b - 1] = r[b - 1]
+        for s in range(b - 2, a - 1, -1):
+            G[s] = r[s] + g * (one_m * Y[s + 1] + lam * G[s + 1])
+    return G
+
+
+def batched_td0_reference(params, records, offs, gamma, lam=0.0):
     """float64 forward and gradient of the batched loss. params: 25,601 values in
     state_dict order; records [m, 12]; offs [E + 1] (episode e = records
-    [offs[e], offs[e + 1]), each at least 1 long). Returns dict(grad float64
+    [offs[e], offs[e + 1]), each at least 1 long). lam != 0: the target is the
+    lambda-return (lambda_returns on the detached Y). Returns dict(grad float64
     [25601], loss, Y float64 [m], target, td_error, predicted_value, reward: the
     last three summed over episodes as the kernel's metrics are)."""
     W1, b1, w2, b2 = (np.asarray(x, np.float64) for x in split_params(params))
@@ -70,6 +96,8 @@ def batched_td0_reference(params, records, offs, gamma):
     last[offs[1:] - 1] = True
     nxt = np.append(Y[1:], 0.0)
     tgt = np.where(last, rew, rew + float(gamma) * nxt)
+    if lam != 0.0:
+        tgt = lambda_returns(Y, rew, offs, gamma, lam)
     T = np.repeat(lens, lens).astype(np.float64)
     diff = Y - tgt
     loss = float((diff * diff / T).sum() / E)

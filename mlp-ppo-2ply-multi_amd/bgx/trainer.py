@@ -22,6 +22,13 @@ runs update_records as bgx_td0_update_batched (csrc/bgx_train_batch.hip: the
 forward and backward passes over all CUs, episodes of any length);
 bgx/train_ref.py restates that update in numpy. The three paths share the
 flat state, so a trainer may change backend between updates.
+
+lam (default 0: TD(0), the reference's target) makes the target the
+lambda-return G_s = r_s + gamma ((1 - lam) Y_{s+1} + lam G_{s+1}) on the detached
+Y, G = r on an episode's last record. The torch backend honours it, sequential
+and batched; batched=True with backend="hip" runs bgx_tdlambda_update_batched
+(the targets computed on the device, csrc/bgx_train_lambda.hip). The
+sequential HIP kernel knows TD(0) only.
 """
 from __future__ import annotations
 
@@ -42,7 +49,7 @@ MIN_EPISODES_TO_TRAIN = 200   # configuration.py:7
 class DeviceTrainer:
     def __init__(self, parameter_manager, device=None, lr=LEARNING_RATE, gamma=GAMMA,
                  grad_clip=GRAD_CLIP_THRESHOLD, batch_episode_size=MIN_EPISODES_TO_TRAIN, batched=False,
-                 backend=None):
+                 backend=None, lam=0.0):
         self.parameter_manager = parameter_manager
         self.device = torch.device(device) if device is not None else torch.device("cuda")
         self.policy_network = BackgammonPolicyNetwork().to(self.device)
@@ -58,6 +65,10 @@ class DeviceTrainer:
         if backend not in ("hip", "torch"):
             raise ValueError(f"backend must be 'hip' or 'torch', not {backend!r}")
         self.backend = backend
+        lam = float(lam)
+        if not 0.0 <= lam <= 1.0:   # a NaN fails it too
+            raise ValueError(f"lam must be in [0, 1], not {lam!r}")
+        self.lam = lam
         self.total_episodes = 0
         self._flat = None   # HIP backend state: params / Adam m / v (flat, state_dict order), step
         self._work = None   # batched HIP backend: the workspace tensor, regrown on demand
@@ -107,6 +118,9 @@ class DeviceTrainer:
         """The same update from compact records (headers [n, 16], records [m, 12],
         each episode's records contiguous in header order); any n >= 1."""
         if self.backend == "hip":
+            if self.lam != 0.0 and not self.batched:
+                raise ValueError("the sequential HIP update (bgx_td0_update) is TD(0) only: for lam != 0 use "
+                                 "batched=True with backend='hip', or backend='torch'")
             return self._update_hip_batched(headers, records) if self.batched else self._update_hip(headers, records)
         return self._update(*self._from_records(headers, records))
 
@@ -194,8 +208,9 @@ class DeviceTrainer:
         return self._finish_hip(metrics, hdr, lens)
 
     def _update_hip_batched(self, headers, records):
-        """One bgx_td0_update_batched call: one Adam step on the mean of the
-        per-episode losses (the torch batched path's semantics)."""
+        """One bgx_td0_update_batched call (bgx_tdlambda_update_batched when
+        lam != 0): one Adam step on the mean of the per-episode losses (the
+        torch batched path's semantics)."""
         import ctypes
         from ._lib import check, lib, ptr, stream_handle
         rec = torch.as_tensor(records).to(self.device)
@@ -215,18 +230,28 @@ class DeviceTrainer:
         offs = torch.as_tensor(offs_h.astype(np.int32), device=self.device)
         f = self._hip_state()
         need = ctypes.c_uint64(0)
-        check(lib().bgx_td0_batch_workspace(n_rec, ctypes.byref(need)), "bgx_td0_batch_workspace")
+        if self.lam != 0.0:
+            check(lib().bgx_tdlambda_batch_workspace(n_rec, ctypes.byref(need)), "bgx_tdlambda_batch_workspace")
+        else:
+            check(lib().bgx_td0_batch_workspace(n_rec, ctypes.byref(need)), "bgx_td0_batch_workspace")
         if self._work is None or self._work.numel() < need.value or self._work.device != f["p"].device:
             self._work = torch.empty(need.value, dtype=torch.uint8, device=self.device)
         metrics = torch.zeros(5, dtype=torch.float64, device=self.device)
         clip = float(self.grad_clip) if self.grad_clip is not None else 0.0
+        lr = float(self.optimizer.param_groups[0]["lr"])
         with torch.cuda.device(self.device):   # the trainer's device and its current stream
-            check(lib().bgx_td0_update_batched(ptr(rec), ptr(offs), n_eps, n_rec, ptr(f["p"]), ptr(f["m"]),
-                                               ptr(f["v"]), ptr(f["step"]),
-                                               float(self.optimizer.param_groups[0]["lr"]), float(self.gamma), clip,
-                                               ptr(metrics), None, ptr(self._work), self._work.numel(),
-                                               stream_handle(torch.cuda.current_stream(self.device))),
-                  "bgx_td0_update_batched")
+            stream = stream_handle(torch.cuda.current_stream(self.device))
+            if self.lam != 0.0:
+                check(lib().bgx_tdlambda_update_batched(ptr(rec), ptr(offs), n_eps, n_rec, ptr(f["p"]), ptr(f["m"]),
+                                                        ptr(f["v"]), ptr(f["step"]), lr, float(self.gamma), self.lam,
+                                                        clip, ptr(metrics), None, None, ptr(self._work),
+                                                        self._work.numel(), stream),
+                      "bgx_tdlambda_update_batched")
+            else:
+                check(lib().bgx_td0_update_batched(ptr(rec), ptr(offs), n_eps, n_rec, ptr(f["p"]), ptr(f["m"]),
+                                                   ptr(f["v"]), ptr(f["step"]), lr, float(self.gamma), clip,
+                                                   ptr(metrics), None, ptr(self._work), self._work.numel(), stream),
+                      "bgx_td0_update_batched")
         return self._finish_hip(metrics, hdr, lens)
 
     def _finish_hip(self, metrics, hdr, lens):
@@ -320,6 +345,12 @@ class DeviceTrainer:
     def _episode_terms(self, obs, rewards, a, b):
         y = self.policy_network(obs[a:b]).squeeze()
         tgt = rewards[a:b].clone().squeeze()
-        if b - a > 1:
+        if self.lam != 0.0:
+            if b - a > 1:   # the serial recurrence in y's dtype, from the episode's end
+                from .train_ref import lambda_returns
+                g = lambda_returns(y.detach().reshape(-1).cpu().numpy(), rewards[a:b].cpu().numpy(), [0, b - a],
+                                   float(self.gamma), self.lam)
+                tgt = torch.from_numpy(g).to(y.device)
+        elif b - a > 1:
             tgt[:-1] += self.gamma * y[1:].detach()
         return y, tgt

@@ -345,20 +345,24 @@ int bgx_td0_batch_shape(int* tile, int* grid) {
     });
 }
 
-int bgx_td0_update_batched(const uint32_t* d_records, const int32_t* d_offs, int n_eps, int n_records,
-                           float* d_params, float* d_adam_m, float* d_adam_v, int* d_step, float lr, float gamma,
-                           float grad_clip, double* d_metrics, float* d_grad_out, void* d_work, uint64_t work_bytes,
-                           void* stream) {
-    return guarded("bgx_td0_update_batched", [&]() -> int {
-        if (n_eps <= 0 || n_records < n_eps)
-            return fail(BGX_E_ARG, "bgx_td0_update_batched: n_eps=%d n_records=%d", n_eps, n_records);
+// the batched update behind both entry points; lam: the TD(lambda) one (its
+// workspace carries the targets after the TD(0) layout)
+static int update_batched(const char* name, bool lam, const uint32_t* d_records, const int32_t* d_offs, int n_eps,
+                          int n_records, float* d_params, float* d_adam_m, float* d_adam_v, int* d_step, float lr,
+                          float gamma, float lambda, float grad_clip, double* d_metrics, float* d_grad_out,
+                          float* d_target_out, void* d_work, uint64_t work_bytes, void* stream) {
+    return guarded(name, [&]() -> int {
+        if (n_eps <= 0 || n_records < n_eps) return fail(BGX_E_ARG, "%s: n_eps=%d n_records=%d", name, n_eps, n_records);
         if (!d_records || !d_offs || !d_params || !d_adam_m || !d_adam_v || !d_step || !d_metrics || !d_work)
-            return fail(BGX_E_ARG, "bgx_td0_update_batched: null pointer");
+            return fail(BGX_E_ARG, "%s: null pointer", name);
+        if (lam && !(lambda >= 0.0f && lambda <= 1.0f))   // a NaN fails both comparisons
+            return fail(BGX_E_ARG, "%s: lambda=%g is not in [0, 1]", name, (double)lambda);
         const bgx::TrainBatchLayout l = bgx::train_batch_layout(n_records);
-        if (work_bytes < l.bytes)
-            return fail(BGX_E_ARG, "bgx_td0_update_batched: work_bytes=%llu < %llu (bgx_td0_batch_workspace)",
-                        (unsigned long long)work_bytes, (unsigned long long)l.bytes);
-        if ((uintptr_t)d_work % 16 != 0) return fail(BGX_E_ARG, "bgx_td0_update_batched: d_work is not 16-byte aligned");
+        const uint64_t need = lam ? l.bytes_lambda : l.bytes;
+        if (work_bytes < need)
+            return fail(BGX_E_ARG, "%s: work_bytes=%llu < %llu (%s)", name, (unsigned long long)work_bytes,
+                        (unsigned long long)need, lam ? "bgx_tdlambda_batch_workspace" : "bgx_td0_batch_workspace");
+        if ((uintptr_t)d_work % 16 != 0) return fail(BGX_E_ARG, "%s: d_work is not 16-byte aligned", name);
         DeviceScope ds(d_params);   // the kernels run on the device holding the parameters
         HIP_TRY(ds.err);
         char* w = (char*)d_work;
@@ -382,9 +386,40 @@ int bgx_td0_update_batched(const uint32_t* d_records, const int32_t* d_offs, int
         a.grad = (float*)(w + l.grad);
         a.mpart = (double*)(w + l.mpart);
         a.sqpart = (double*)(w + l.sqpart);
+        if (lam) {
+            a.lambda = lambda;
+            a.tgt = (float*)(w + l.tgt);
+            a.target_out = d_target_out;
+        }
         HIP_TRY(bgx_launch_td0_batched(&a, (hipStream_t)stream));
         return BGX_OK;
     });
+}
+
+int bgx_td0_update_batched(const uint32_t* d_records, const int32_t* d_offs, int n_eps, int n_records,
+                           float* d_params, float* d_adam_m, float* d_adam_v, int* d_step, float lr, float gamma,
+                           float grad_clip, double* d_metrics, float* d_grad_out, void* d_work, uint64_t work_bytes,
+                           void* stream) {
+    return update_batched("bgx_td0_update_batched", false, d_records, d_offs, n_eps, n_records, d_params, d_adam_m,
+                          d_adam_v, d_step, lr, gamma, 0.0f, grad_clip, d_metrics, d_grad_out, nullptr, d_work,
+                          work_bytes, stream);
+}
+
+int bgx_tdlambda_batch_workspace(int n_records, uint64_t* bytes) {
+    return guarded("bgx_tdlambda_batch_workspace", [&]() -> int {
+        if (n_records <= 0 || !bytes) return fail(BGX_E_ARG, "bgx_tdlambda_batch_workspace: n_records=%d", n_records);
+        *bytes = bgx::train_batch_layout(n_records).bytes_lambda;
+        return BGX_OK;
+    });
+}
+
+int bgx_tdlambda_update_batched(const uint32_t* d_records, const int32_t* d_offs, int n_eps, int n_records,
+                                float* d_params, float* d_adam_m, float* d_adam_v, int* d_step, float lr,
+                                float gamma, float lambda, float grad_clip, double* d_metrics, float* d_grad_out,
+                                float* d_target_out, void* d_work, uint64_t work_bytes, void* stream) {
+    return update_batched("bgx_tdlambda_update_batched", true, d_records, d_offs, n_eps, n_records, d_params,
+                          d_adam_m, d_adam_v, d_step, lr, gamma, lambda, grad_clip, d_metrics, d_grad_out,
+                          d_target_out, d_work, work_bytes, stream);
 }
 
 int bgx_reply_moves(const uint8_t* d_boards, const uint8_t* d_opponent, int n, uint32_t* d_out, int cap,

@@ -323,10 +323,15 @@ struct TrainBatchArgs {
     double* mpart;               // [TRAIN_BATCH_GRID][4] metric shares per workgroup
     double* sqpart;              // [TRAIN_BATCH_SQ]
     int n_tiles, grid;           // set by the launcher
+    // TD(lambda) (bgx_tdlambda_update_batched); tgt null: the TD(0) call, its five launches as they were
+    float lambda;                // in [0, 1]
+    float* tgt;                  // workspace [n_rec]: the lambda-return G of every record (bgx_train_lambda.hip)
+    float* target_out;           // null, or [n_rec]: a copy of tgt for the caller
 };
-// byte offsets of the workspace's parts (each 16-byte aligned) and its size
+// byte offsets of the workspace's parts (each 16-byte aligned) and its size;
+// tgt follows the TD(0) call's workspace (bytes), bytes_lambda includes it
 struct TrainBatchLayout {
-    uint64_t Y, info, partial, grad, mpart, sqpart, bytes;
+    uint64_t Y, info, partial, grad, mpart, sqpart, bytes, tgt, bytes_lambda;
 };
 inline TrainBatchLayout train_batch_layout(int n_rec) {
     const uint64_t n4 = ((uint64_t)n_rec + 3) / 4 * 4;
@@ -338,6 +343,8 @@ inline TrainBatchLayout train_batch_layout(int n_rec) {
     l.mpart = l.grad + (uint64_t)TRAIN_BATCH_PSTRIDE * 4;
     l.sqpart = l.mpart + (uint64_t)TRAIN_BATCH_GRID * 4 * 8;
     l.bytes = l.sqpart + (uint64_t)TRAIN_BATCH_SQ * 8;
+    l.tgt = l.bytes;
+    l.bytes_lambda = l.tgt + 4 * n4;
     return l;
 }
 
@@ -382,6 +389,9 @@ hipError_t bgx_launch_top5(const float* V, const int32_t* job_off, const int32_t
 hipError_t bgx_launch_two_ply_reduce(const float* job_val, int n, double* out, hipStream_t stream);
 hipError_t bgx_launch_td0(const bgx::TrainArgs* args, hipStream_t stream);
 hipError_t bgx_launch_td0_batched(const bgx::TrainBatchArgs* args, hipStream_t stream);
+// tgt[s] (and target_out[s]) = the lambda-return of every record in an episode, 0 elsewhere;
+// reads Y, so it goes between the forward and the backward launch (bgx_train_lambda.hip)
+hipError_t bgx_launch_lambda_targets(const bgx::TrainBatchArgs* args, hipStream_t stream);
 // harvest: episode offsets / totals (info[4] on the device, hinfo[4] host-mapped
 // or null), then the headers + records gather (persistent grid; the episode
 // count is read on the device)

@@ -20,6 +20,9 @@
 //   adam      norm, clip coefficient and the Adam step over the parameters
 // Every sum has a fixed order (no float atomics): the same inputs give the same
 // bits on every call.
+// bgx_tdlambda_update_batched (TrainBatchArgs::tgt set) is the same call with the
+// lambda-return as the target: the target stage of bgx_train_lambda.hip runs
+// between forward and backward, and the backward launch reads tgt[s].
 //
 // Both GEMMs run on the f32-input MFMA (v_mfma_f32_32x32x2_f32: an exact k-ordered
 // fp32 fma chain, so no weight scaling and no dh underflow). A workgroup is 4
@@ -230,6 +233,8 @@ __global__ __launch_bounds__(TB_T) void tb_forward_kernel(TrainBatchArgs a) {
 }
 
 // ---------------------------------------------------------------- backward
+// LAM: the target is the target stage's tgt[s] (TD(lambda)), not the inline TD(0) one
+template <bool LAM>
 __global__ __launch_bounds__(TB_T) void tb_backward_kernel(TrainBatchArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t RW[TB_TILE][8];
     __shared__ __attribute__((aligned(16))) float D[TB_TILE];   // dL/dY of the tile's records
@@ -284,8 +289,13 @@ __global__ __launch_bounds__(TB_T) void tb_backward_kernel(TrainBatchArgs a) {
                 if (T > 0) {
                     const float rew = __uint_as_float(a.rec[(size_t)s * 12 + 9]);
                     const float y = a.Y[s];
-                    const bool boot = inf >= 0 && s + 1 < a.n_rec;
-                    const float tg = boot ? rew + a.gamma * a.Y[s + 1] : rew;
+                    float tg;
+                    if constexpr (LAM) {
+                        tg = a.tgt[s];
+                    } else {
+                        const bool boot = inf >= 0 && s + 1 < a.n_rec;
+                        tg = boot ? rew + a.gamma * a.Y[s + 1] : rew;
+                    }
                     const float diff = y - tg, fT = (float)T;
                     d = 2.0f * diff / (n_eps * fT);
                     m_loss += (double)(diff * diff / fT);
@@ -427,7 +437,16 @@ extern "C" hipError_t bgx_launch_td0_batched(const bgx::TrainBatchArgs* args, hi
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(tb_index_kernel, dim3((a.n_eps + TB_T - 1) / TB_T), dim3(TB_T), 0, stream, a);
     hipLaunchKernelGGL(tb_forward_kernel, dim3(a.grid), dim3(TB_T), 0, stream, a);
-    hipLaunchKernelGGL(tb_backward_kernel, dim3(a.grid), dim3(TB_T), 0, stream, a);
+    // TD(lambda): the target stage, then the backward launch on its targets. lambda = 0
+    // keeps the TD(0) backward launch (the same bits by construction); the stage then
+    // runs only to fill target_out
+    const bool lam = a.tgt && a.lambda != 0.0f;
+    if (lam || (a.tgt && a.target_out)) {
+        e = bgx_launch_lambda_targets(&a, stream);
+        if (e != hipSuccess) return e;
+    }
+    if (lam) hipLaunchKernelGGL(tb_backward_kernel<true>, dim3(a.grid), dim3(TB_T), 0, stream, a);
+    else hipLaunchKernelGGL(tb_backward_kernel<false>, dim3(a.grid), dim3(TB_T), 0, stream, a);
     hipLaunchKernelGGL(tb_reduce_kernel, dim3(TB_NB), dim3(TB_T), 0, stream, a);
     hipLaunchKernelGGL(tb_adam_kernel, dim3(TB_NB), dim3(TB_T), 0, stream, a);
     return hipGetLastError();

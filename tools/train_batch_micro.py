@@ -3,6 +3,8 @@
 episodes (repeated to reach the larger sizes), then per size
 
   batched_hip   one bgx_td0_update_batched call, event-timed on the stream
+  lambda_hip    (--lam L) one bgx_tdlambda_update_batched call on the same
+                records in the same process, event-timed the same way
   sequential    one bgx_td0_update call on the same records, event-timed
   batched_torch DeviceTrainer(batched=True, backend="torch").update_records,
                 wall clock around a synchronize (an eager path: its host work
@@ -81,6 +83,8 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--only", choices=("hip",), default=None)
     ap.add_argument("--torch-max-reps", type=int, default=5)
+    ap.add_argument("--lam", type=float, default=None,
+                    help="also time bgx_tdlambda_update_batched with this lambda beside the TD(0) call")
     args = ap.parse_args()
     dev = torch.device("cuda")
     torch.manual_seed(0)
@@ -110,6 +114,21 @@ def main():
         row["batched_hip"] = {"ms": ms, "episodes_per_s": n_eps / ms * 1e3, "records_per_s": n_rec / ms * 1e3,
                               "tflops": n_rec * FLOP_PER_RECORD / ms * 1e-9,
                               "of_f32_mfma_peak": n_rec * FLOP_PER_RECORD / ms * 1e-9 / PEAK_TF}
+        if args.lam is not None:
+            # ---- the TD(lambda) call: the same launches and the target stage between forward and backward
+            p, m, v, step = flat_state(pm, dev)
+            need_l = ctypes.c_uint64(0)
+            check(L.bgx_tdlambda_batch_workspace(n_rec, ctypes.byref(need_l)))
+            work_l = torch.empty(need_l.value, dtype=torch.uint8, device=dev)
+
+            def batched_lambda():
+                check(L.bgx_tdlambda_update_batched(ptr(rec), ptr(offs), n_eps, n_rec, ptr(p), ptr(m), ptr(v),
+                                                    ptr(step), 1e-3, 0.99, args.lam, 1.0, ptr(met), None, None,
+                                                    ptr(work_l), need_l.value, s))
+
+            ms_l = event_ms(batched_lambda, args.reps)
+            row["lambda_hip"] = {"lam": args.lam, "ms": ms_l, "episodes_per_s": n_eps / ms_l * 1e3,
+                                 "records_per_s": n_rec / ms_l * 1e3, "over_td0": ms_l / ms}
         if args.only is None:
             # ---- the sequential kernel (one Adam step per episode)
             p, m, v, step = flat_state(pm, dev)

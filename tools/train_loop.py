@@ -2,7 +2,8 @@
 """Self-play + training on one GPU without Python Episode objects (SURVEY §8f
 rows 1-3 together): the engine plays, every finished episode's compact
 records feed DeviceTrainer.update_records in the reference's batches of 200
-(--episodes-per-update N for others; --batched --backend hip for the multi-CU update),
+(--episodes-per-update N for others; --batched --backend hip for the multi-CU update;
+--lam L for TD(lambda) targets, with --batched --backend hip or --backend torch),
 and each update's weights go straight back into the engine with the
 reference temperature schedule (ParameterManager.get_temperature)."""
 import argparse
@@ -49,11 +50,14 @@ def main():
                     help="unset: hip for the sequential update, torch for --batched (DeviceTrainer's rule)")
     ap.add_argument("--episodes-per-update", type=int, default=200, metavar="N",
                     help="episodes per trainer update (the reference's batch is 200)")
+    ap.add_argument("--lam", type=float, default=0.0,
+                    help="lambda of the lambda-return targets (0: TD(0), the reference's)")
     args = ap.parse_args()
     per = args.episodes_per_update
     torch.manual_seed(0)
     pm = LocalPM(BackgammonPolicyNetwork().state_dict())
-    trainer = DeviceTrainer(pm, device="cuda", batch_episode_size=per, batched=args.batched, backend=args.backend)
+    trainer = DeviceTrainer(pm, device="cuda", batch_episode_size=per, batched=args.batched, backend=args.backend,
+                            lam=args.lam)
     eng = Engine(lanes=args.lanes, seed=0)
     w = dict(zip(("W1", "b1", "w2", "b2"), weights_from(pm.get_parameters())))
     eng.set_weights(w, pm.get_temperature(), pm.version)
@@ -84,7 +88,7 @@ def main():
                       "wall_s": el, "train_s": t_train, "updates_per_s": done / el,
                       "train_episodes_per_s": per * done / t_train, "train_share": t_train / el, "last_loss": m["loss"],
                       "version": pm.version, "temperature": pm.get_temperature(), "batched": args.batched,
-                      "backend": trainer.backend, "episodes_per_update": per}))
+                      "backend": trainer.backend, "episodes_per_update": per, "lam": trainer.lam}))
 
 
 if __name__ == "__main__":
