@@ -464,6 +464,41 @@ int bgx_tdlambda_update_batched(const uint32_t* d_records, const int32_t* d_offs
  * records (bgx_td0_batch_workspace plus G of every record); pure host arithmetic */
 int bgx_tdlambda_batch_workspace(int n_records, uint64_t* bytes);
 
+/* bgx_tdlambda_update_batched with options (flags: BGX_TDF_* bits; 0 is
+ * bgx_tdlambda_update_batched itself, bit for bit).
+ * BGX_TDF_ZERO_SUM: the target takes the next record from the opponent's side
+ * where the mover changes, as the engine uses V (1-ply picks argmax V under the
+ * mover's indicator; 2-ply counts the opponent's value against the mover). With
+ * m_s the mover of record s (word 11 bit 9; in engine records also the
+ * indicator, word 6 bit 16), f_s = m_s ^ m_{s+1} for s < b-1 (consecutive
+ * records share a mover when the opponent passed: passes write no record) and
+ * B_s(x) = 1 - x if f_s, else x, on the detached Y:
+ *   G_{b-1} = r_{b-1},
+ *   G_s = r_s + gamma ((1 - lambda) B_s(Y_{s+1}) + lambda B_s(G_{s+1})),  a <= s < b-1,
+ *   loss = (1/E) sum_e (1/T_e) sum_s (Y_s - G_s)^2.
+ * The complement is 1 - x (the value head is a sum of sigmoid activations), the
+ * rewards are unchanged. lambda = 0 gives r_s + gamma B_s(Y_{s+1}); with no
+ * mover change anywhere G is bgx_tdlambda_update_batched's, bit for bit. The
+ * target stage's zero-sum instance (csrc/bgx_train_lambda.hip: the same scan on
+ * sign-folded terms, one fixed fma chain per record, no episode-length limit;
+ * from an episode's last mover change towards its start the powers of
+ * gamma lambda are double products rounded once, nearer the end the plain
+ * instance's, so an episode without a mover change keeps its bits)
+ * runs at every lambda, also at 0, and the backward launch reads its G; the
+ * forward, backward, reduce and Adam launches are bgx_tdlambda_update_batched's.
+ * Workspace: bgx_tdlambda_batch_workspace(n_records). d_target_out, the
+ * metrics, determinism, asynchrony (no host synchronisation, no allocation,
+ * capturable) as bgx_tdlambda_update_batched.
+ * BGX_E_ARG: what bgx_tdlambda_update_batched rejects, and any flags bit other
+ * than BGX_TDF_ZERO_SUM; all before the device is touched. */
+#define BGX_TDF_ZERO_SUM 1u
+int bgx_td_update_batched(const uint32_t* d_records, const int32_t* d_offs, int n_eps, int n_records,
+                          float* d_params, float* d_adam_m, float* d_adam_v, int* d_step,
+                          float lr, float gamma, float lambda, uint32_t flags, float grad_clip, double* d_metrics,
+                          float* d_grad_out   /* NULL, or [25601]: the pre-clip gradient, state_dict order */,
+                          float* d_target_out /* NULL, or [n_records]: G of every record */,
+                          void* d_work, uint64_t work_bytes, void* stream);
+
 /* Copy-engine transfer helpers (bgx/hostgather.py: the episode gather of
  * the ranks of one node through host shared memory, replacing the pickled
  * queue of src/main.py:115-133 / multi/experience_queue.py:5-13 without

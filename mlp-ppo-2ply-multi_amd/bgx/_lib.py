@@ -95,6 +95,9 @@ SIGNATURES = {
                                             c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_u64, c_void_p]),
     "bgx_tdlambda_batch_workspace": (c_int, [c_int, ctypes.POINTER(c_u64)]),
+    "bgx_td_update_batched": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_float, c_float, c_float, ctypes.c_uint32, c_float, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_u64, c_void_p]),
     "bgx_host_register": (c_int, [c_void_p, c_u64]),
     "bgx_host_unregister": (c_int, [c_void_p]),
     "bgx_copy_async": (c_int, [c_void_p, c_void_p, c_u64, c_int, c_void_p]),

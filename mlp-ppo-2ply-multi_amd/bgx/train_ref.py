@@ -6,7 +6,9 @@ use. No torch, no GPU, no libbgx.so.
     tgt_s = r_s + gamma Y_{s+1} (detached; r_s alone on an episode's last record)
 
 and of its TD(lambda) form (bgx_tdlambda_update_batched), whose target is the
-lambda-return of lambda_returns. batched_td0_reference states the forward pass and the gradient in float64;
+lambda-return of lambda_returns, with the zero-sum targets of
+bgx_td_update_batched (BGX_TDF_ZERO_SUM) as lambda_returns(movers=) /
+batched_td0_reference(zero_sum=True). batched_td0_reference states the forward pass and the gradient in float64;
 adam_reference states clip_grad_norm_ and the Adam step in float32, in the
 kernel's operation order, which is torch's (sqrt(v) / sqrt(bc2) + eps, then
 p + (-step_size m) / den, every operation correctly rounded).
@@ -50,35 +52,54 @@ def split_params(params):
     return p[:N_W1].reshape(128, 198), p[N_W1:N_W1 + 128], p[N_W1 + 128:N_W1 + 256], p[N_W1 + 256]
 
 
-def lambda_returns(Y, rewards, offs, gamma, lam):
+def record_movers(records) -> np.ndarray:
+    """int64 [m]: the mover of each record (word 11 bit 9, bgx/records.py)."""
+    r = np.ascontiguousarray(records).view(np.uint32).reshape(-1, 12)
+    return ((r[:, 11] >> 9) & 1).astype(np.int64)
+
+
+def lambda_returns(Y, rewards, offs, gamma, lam, movers=None):
     """The lambda-return of every record, the serial recurrence from each
     episode's end in the dtype of Y (float64: the checker; float32: the fp32
     comparison, every operation rounded to float32):
         G_{b-1} = r_{b-1},  G_s = r_s + gamma ((1 - lam) Y_{s+1} + lam G_{s+1}).
     A record in no episode keeps 0. lam = 0 is the TD(0) target, lam = 1 the
-    discounted Monte-Carlo return (Y then enters with weight 0)."""
+    discounted Monte-Carlo return (Y then enters with weight 0).
+    movers ([m], the mover of each record): the zero-sum target
+    (bgx_td_update_batched, BGX_TDF_ZERO_SUM). Where the mover changes from
+    record s to s + 1 both Y_{s+1} and G_{s+1} enter from the opponent's side,
+    as 1 - x:
+        G_s = r_s + gamma ((1 - lam) (1 - Y_{s+1}) + lam (1 - G_{s+1})).
+    None, or one mover everywhere: the plain return, bit for bit."""
     Y = np.asarray(Y)
     dt = Y.dtype.type
     r = np.asarray(rewards).astype(dt)
     g, lam = dt(gamma), dt(lam)
-    one_m = dt(1.0) - lam
+    one_m, one = dt(1.0) - lam, dt(1.0)
     G = np.zeros(len(Y), dt)
     offs = np.asarray(offs, np.int64)
+    mv = None if movers is None else np.asarray(movers).astype(np.int64)
+    if mv is not None and len(mv) != len(Y):
+        raise ValueError(f"movers: expected {len(Y)} values, got {len(mv)}")
     for e in range(len(offs) - 1):
         a, b = int(offs[e]), int(offs[e + 1])
         if b <= a:
             continue
         G[b - 1] = r[b - 1]
         for s in range(b - 2, a - 1, -1):
-            G[s] = r[s] + g * (one_m * Y[s + 1] + lam * G[s + 1])
+            if mv is not None and mv[s] != mv[s + 1]:
+                G[s] = r[s] + g * (one_m * (one - Y[s + 1]) + lam * (one - G[s + 1]))
+            else:
+                G[s] = r[s] + g * (one_m * Y[s + 1] + lam * G[s + 1])
     return G
 
 
-def batched_td0_reference(params, records, offs, gamma, lam=0.0):
+def batched_td0_reference(params, records, offs, gamma, lam=0.0, zero_sum=False):
     """float64 forward and gradient of the batched loss. params: 25,601 values in
     state_dict order; records [m, 12]; offs [E + 1] (episode e = records
     [offs[e], offs[e + 1]), each at least 1 long). lam != 0: the target is the
-    lambda-return (lambda_returns on the detached Y). Returns dict(grad float64
+    lambda-return (lambda_returns on the detached Y). zero_sum: the zero-sum
+    target at every lam (lambda_returns with the movers of word 11). Returns dict(grad float64
     [25601], loss, Y float64 [m], target, td_error, predicted_value, reward: the
     last three summed over episodes as the kernel's metrics are)."""
     W1, b1, w2, b2 = (np.asarray(x, np.float64) for x in split_params(params))
@@ -96,9 +117,11 @@ def batched_td0_reference(params, records, offs, gamma, lam=0.0):
     last[offs[1:] - 1] = True
     nxt = np.append(Y[1:], 0.0)
     tgt = np.where(last, rew, rew + float(gamma) * nxt)
-    if lam != 0.0:
+    if zero_sum:
+        tgt = lambda_returns(Y, rew, offs, gamma, lam, movers=record_movers(r))
+    elif lam != 0.0:
         tgt = lambda_returns(Y, rew, offs, gamma, lam)
-    T = np.repeat(lens, lens).astype(np.float64)
+    T =np.repeat(lens, lens).astype(np.float64)
     diff = Y - tgt
     loss = float((diff * diff / T).sum() / E)
     d = 2.0 * diff / (E * T)

@@ -29,6 +29,21 @@ Y, G = r on an episode's last record. The torch backend honours it, sequential
 and batched; batched=True with backend="hip" runs bgx_tdlambda_update_batched
 (the targets computed on the device, csrc/bgx_train_lambda.hip). The
 sequential HIP kernel knows TD(0) only.
+
+zero_sum (default False: the reference's target, which adds the next record's
+value with a plus sign whoever moves there) makes the target agree with how the
+engine uses V, the value for the player whose indicator is set: where the mover
+changes from record s to s + 1, Y_{s+1} and G_{s+1} enter from the opponent's
+side, as 1 - x:
+    G_s = r_s + gamma ((1 - lam) B_s(Y_{s+1}) + lam B_s(G_{s+1})),
+    B_s(x) = 1 - x if mover_s != mover_{s+1} else x
+(consecutive records share a mover when the opponent passed). The movers come
+from word 11 bit 9 of the records, or from feature 197 (the indicator of player
+1) of an Episode's observations: the same bit in engine records. The torch
+backend honours it, sequential and batched; batched=True with backend="hip"
+runs bgx_td_update_batched with BGX_TDF_ZERO_SUM (the zero-sum instance of the
+target stage, at every lam). The sequential HIP kernel stays the reference's
+TD(0).
 """
 from __future__ import annotations
 
@@ -38,6 +53,8 @@ import torch.nn.functional as F
 
 from . import ops
 from .records import WIN_TYPES
+
+TDF_ZERO_SUM = 1   # BGX_TDF_ZERO_SUM (include/bgx.h)
 from .net import BackgammonPolicyNetwork
 
 LEARNING_RATE = 1e-3          # config/configuration.py:17
@@ -49,7 +66,7 @@ MIN_EPISODES_TO_TRAIN = 200   # configuration.py:7
 class DeviceTrainer:
     def __init__(self, parameter_manager, device=None, lr=LEARNING_RATE, gamma=GAMMA,
                  grad_clip=GRAD_CLIP_THRESHOLD, batch_episode_size=MIN_EPISODES_TO_TRAIN, batched=False,
-                 backend=None, lam=0.0):
+                 backend=None, lam=0.0, zero_sum=False):
         self.parameter_manager = parameter_manager
         self.device = torch.device(device) if device is not None else torch.device("cuda")
         self.policy_network = BackgammonPolicyNetwork().to(self.device)
@@ -69,6 +86,9 @@ class DeviceTrainer:
         if not 0.0 <= lam <= 1.0:   # a NaN fails it too
             raise ValueError(f"lam must be in [0, 1], not {lam!r}")
         self.lam = lam
+        if not isinstance(zero_sum, (bool, np.bool_)):
+            raise ValueError(f"zero_sum must be a bool, not {zero_sum!r}")
+        self.zero_sum = bool(zero_sum)
         self.total_episodes = 0
         self._flat = None   # HIP backend state: params / Adam m / v (flat, state_dict order), step
         self._work = None   # batched HIP backend: the workspace tensor, regrown on demand
@@ -84,7 +104,7 @@ class DeviceTrainer:
 
     # ------------------------------------------------------------ inputs
     def _from_records(self, headers, records):
-        """(observations [m, 198], rewards [m], episode lengths, win types) on the device."""
+        """(observations [m, 198], rewards [m], episode lengths, win types, movers [m]) on the device."""
         rec = torch.as_tensor(records).to(self.device)
         if rec.dtype != torch.int32:
             rec = rec.view(torch.int32) if rec.dtype == torch.uint32 else rec.to(torch.int32)
@@ -95,7 +115,17 @@ class DeviceTrainer:
         hdr = np.asarray(torch.as_tensor(headers).cpu().numpy()).astype(np.uint32)
         lens = hdr[:, 3].astype(np.int64).tolist()
         wins = [WIN_TYPES[int(w) & 0xFF] for w in (hdr[:, 5] & 0xFF).tolist()]
-        return obs, rewards, lens, wins
+        return obs, rewards, lens, wins, self._record_movers(rec)
+
+    @staticmethod
+    def _record_movers(rec):
+        """int32 [m]: the mover of each record, word 11 bit 9 (bgx/records.py)."""
+        return (rec[:, 11] >> 9) & 1
+
+    @staticmethod
+    def _observation_movers(obs):
+        """int32 [m]: feature 197, the indicator of player 1 (the mover in engine records)."""
+        return (obs[:, 197] != 0).to(torch.int32)
 
     def _from_episodes(self, episodes):
         obs, rew, lens, wins = [], [], [], []
@@ -105,7 +135,8 @@ class DeviceTrainer:
             lens.append(len(ep.experiences))
             wins.append(ep.win_type)
         obs_t = torch.stack(obs).to(self.device) if obs else torch.zeros((0, 198), device=self.device)
-        return obs_t, torch.tensor(rew, dtype=torch.float32, device=self.device), lens, wins
+        return (obs_t, torch.tensor(rew, dtype=torch.float32, device=self.device), lens, wins,
+                self._observation_movers(obs_t))
 
     # ------------------------------------------------------------ update
     def update(self, episodes):
@@ -121,6 +152,9 @@ class DeviceTrainer:
             if self.lam != 0.0 and not self.batched:
                 raise ValueError("the sequential HIP update (bgx_td0_update) is TD(0) only: for lam != 0 use "
                                  "batched=True with backend='hip', or backend='torch'")
+            if self.zero_sum and not self.batched:
+                raise ValueError("the sequential HIP update (bgx_td0_update) keeps the reference's TD(0) target: for "
+                                 "zero_sum=True use batched=True with backend='hip', or backend='torch'")
             return self._update_hip_batched(headers, records) if self.batched else self._update_hip(headers, records)
         return self._update(*self._from_records(headers, records))
 
@@ -209,8 +243,9 @@ class DeviceTrainer:
 
     def _update_hip_batched(self, headers, records):
         """One bgx_td0_update_batched call (bgx_tdlambda_update_batched when
-        lam != 0): one Adam step on the mean of the per-episode losses (the
-        torch batched path's semantics)."""
+        lam != 0, bgx_td_update_batched with BGX_TDF_ZERO_SUM when zero_sum):
+        one Adam step on the mean of the per-episode losses (the torch batched
+        path's semantics)."""
         import ctypes
         from ._lib import check, lib, ptr, stream_handle
         rec = torch.as_tensor(records).to(self.device)
@@ -230,7 +265,7 @@ class DeviceTrainer:
         offs = torch.as_tensor(offs_h.astype(np.int32), device=self.device)
         f = self._hip_state()
         need = ctypes.c_uint64(0)
-        if self.lam != 0.0:
+        if self.lam != 0.0 or self.zero_sum:
             check(lib().bgx_tdlambda_batch_workspace(n_rec, ctypes.byref(need)), "bgx_tdlambda_batch_workspace")
         else:
             check(lib().bgx_td0_batch_workspace(n_rec, ctypes.byref(need)), "bgx_td0_batch_workspace")
@@ -241,7 +276,13 @@ class DeviceTrainer:
         lr = float(self.optimizer.param_groups[0]["lr"])
         with torch.cuda.device(self.device):   # the trainer's device and its current stream
             stream = stream_handle(torch.cuda.current_stream(self.device))
-            if self.lam != 0.0:
+            if self.zero_sum:
+                check(lib().bgx_td_update_batched(ptr(rec), ptr(offs), n_eps, n_rec, ptr(f["p"]), ptr(f["m"]),
+                                                  ptr(f["v"]), ptr(f["step"]), lr, float(self.gamma), self.lam,
+                                                  TDF_ZERO_SUM, clip, ptr(metrics), None, None, ptr(self._work),
+                                                  self._work.numel(), stream),
+                      "bgx_td_update_batched")
+            elif self.lam != 0.0:
                 check(lib().bgx_tdlambda_update_batched(ptr(rec), ptr(offs), n_eps, n_rec, ptr(f["p"]), ptr(f["m"]),
                                                         ptr(f["v"]), ptr(f["step"]), lr, float(self.gamma), self.lam,
                                                         clip, ptr(metrics), None, None, ptr(self._work),
@@ -274,7 +315,7 @@ class DeviceTrainer:
         out["episodes"] = n_eps
         return out
 
-    def _update(self, obs, rewards, lens, wins):
+    def _update(self, obs, rewards, lens, wins, movers=None):
         if self._flat is not None:   # continue from the HIP backend's state
             self._sync_module()
             self._flat = None
@@ -291,7 +332,7 @@ class DeviceTrainer:
         if self.batched:
             losses, ys, tgts = [], [], []
             for e in range(n_eps):
-                y, tgt = self._episode_terms(obs, rewards, offs[e], offs[e + 1])
+                y, tgt = self._episode_terms(obs, rewards, offs[e], offs[e + 1], movers)
                 losses.append(F.mse_loss(y, tgt))
                 ys.append(y.detach().reshape(-1))
                 tgts.append(tgt.reshape(-1))
@@ -314,7 +355,7 @@ class DeviceTrainer:
             acc[4] = rewards[:offs[-1]].sum().double()
         else:
             for e in range(n_eps):
-                y, tgt = self._episode_terms(obs, rewards, offs[e], offs[e + 1])
+                y, tgt = self._episode_terms(obs, rewards, offs[e], offs[e + 1], movers)
                 loss = F.mse_loss(y, tgt)
                 opt.zero_grad()
                 loss.backward()
@@ -342,14 +383,19 @@ class DeviceTrainer:
         out["episodes"] = n_eps
         return out
 
-    def _episode_terms(self, obs, rewards, a, b):
+    def _episode_terms(self, obs, rewards, a, b, movers=None):
+        """(Y with its graph, the detached target) of the episode of records a .. b-1;
+        movers [m]: every record's mover, read when zero_sum is set."""
         y = self.policy_network(obs[a:b]).squeeze()
         tgt = rewards[a:b].clone().squeeze()
-        if self.lam != 0.0:
+        if self.zero_sum and movers is None:
+            raise ValueError("zero_sum=True needs the records' movers")
+        if self.lam != 0.0 or self.zero_sum:
             if b - a > 1:   # the serial recurrence in y's dtype, from the episode's end
                 from .train_ref import lambda_returns
+                mv = movers[a:b].cpu().numpy() if self.zero_sum else None
                 g = lambda_returns(y.detach().reshape(-1).cpu().numpy(), rewards[a:b].cpu().numpy(), [0, b - a],
-                                   float(self.gamma), self.lam)
+                                   float(self.gamma), self.lam, movers=mv)
                 tgt = torch.from_numpy(g).to(y.device)
         elif b - a > 1:
             tgt[:-1] += self.gamma * y[1:].detach()

@@ -346,17 +346,19 @@ int bgx_td0_batch_shape(int* tile, int* grid) {
 }
 
 // the batched update behind both entry points; lam: the TD(lambda) one (its
-// workspace carries the targets after the TD(0) layout)
+// workspace carries the targets after the TD(0) layout); flags: BGX_TDF_* (the
+// lambda one only)
 static int update_batched(const char* name, bool lam, const uint32_t* d_records, const int32_t* d_offs, int n_eps,
                           int n_records, float* d_params, float* d_adam_m, float* d_adam_v, int* d_step, float lr,
-                          float gamma, float lambda, float grad_clip, double* d_metrics, float* d_grad_out,
-                          float* d_target_out, void* d_work, uint64_t work_bytes, void* stream) {
+                          float gamma, float lambda, uint32_t flags, float grad_clip, double* d_metrics,
+                          float* d_grad_out, float* d_target_out, void* d_work, uint64_t work_bytes, void* stream) {
     return guarded(name, [&]() -> int {
         if (n_eps <= 0 || n_records < n_eps) return fail(BGX_E_ARG, "%s: n_eps=%d n_records=%d", name, n_eps, n_records);
         if (!d_records || !d_offs || !d_params || !d_adam_m || !d_adam_v || !d_step || !d_metrics || !d_work)
             return fail(BGX_E_ARG, "%s: null pointer", name);
         if (lam && !(lambda >= 0.0f && lambda <= 1.0f))   // a NaN fails both comparisons
             return fail(BGX_E_ARG, "%s: lambda=%g is not in [0, 1]", name, (double)lambda);
+        if (flags & ~(uint32_t)BGX_TDF_ZERO_SUM) return fail(BGX_E_ARG, "%s: unknown flags=0x%x", name, (unsigned)flags);
         const bgx::TrainBatchLayout l = bgx::train_batch_layout(n_records);
         const uint64_t need = lam ? l.bytes_lambda : l.bytes;
         if (work_bytes < need)
@@ -390,6 +392,7 @@ static int update_batched(const char* name, bool lam, const uint32_t* d_records,
             a.lambda = lambda;
             a.tgt = (float*)(w + l.tgt);
             a.target_out = d_target_out;
+            a.zero_sum = (flags & BGX_TDF_ZERO_SUM) ? 1 : 0;
         }
         HIP_TRY(bgx_launch_td0_batched(&a, (hipStream_t)stream));
         return BGX_OK;
@@ -401,7 +404,7 @@ int bgx_td0_update_batched(const uint32_t* d_records, const int32_t* d_offs, int
                            float grad_clip, double* d_metrics, float* d_grad_out, void* d_work, uint64_t work_bytes,
                            void* stream) {
     return update_batched("bgx_td0_update_batched", false, d_records, d_offs, n_eps, n_records, d_params, d_adam_m,
-                          d_adam_v, d_step, lr, gamma, 0.0f, grad_clip, d_metrics, d_grad_out, nullptr, d_work,
+                          d_adam_v, d_step, lr, gamma, 0.0f, 0u, grad_clip, d_metrics, d_grad_out, nullptr, d_work,
                           work_bytes, stream);
 }
 
@@ -418,8 +421,17 @@ int bgx_tdlambda_update_batched(const uint32_t* d_records, const int32_t* d_offs
                                 float gamma, float lambda, float grad_clip, double* d_metrics, float* d_grad_out,
                                 float* d_target_out, void* d_work, uint64_t work_bytes, void* stream) {
     return update_batched("bgx_tdlambda_update_batched", true, d_records, d_offs, n_eps, n_records, d_params,
-                          d_adam_m, d_adam_v, d_step, lr, gamma, lambda, grad_clip, d_metrics, d_grad_out,
+                          d_adam_m, d_adam_v, d_step, lr, gamma, lambda, 0u, grad_clip, d_metrics, d_grad_out,
                           d_target_out, d_work, work_bytes, stream);
+}
+
+int bgx_td_update_batched(const uint32_t* d_records, const int32_t* d_offs, int n_eps, int n_records,
+                          float* d_params, float* d_adam_m, float* d_adam_v, int* d_step, float lr, float gamma,
+                          float lambda, uint32_t flags, float grad_clip, double* d_metrics, float* d_grad_out,
+                          float* d_target_out, void* d_work, uint64_t work_bytes, void* stream) {
+    return update_batched("bgx_td_update_batched", true, d_records, d_offs, n_eps, n_records, d_params, d_adam_m,
+                          d_adam_v, d_step, lr, gamma, lambda, flags, grad_clip, d_metrics, d_grad_out, d_target_out,
+                          d_work, work_bytes, stream);
 }
 
 int bgx_reply_moves(const uint8_t* d_boards, const uint8_t* d_opponent, int n, uint32_t* d_out, int cap,

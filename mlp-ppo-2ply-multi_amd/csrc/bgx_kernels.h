@@ -327,6 +327,9 @@ struct TrainBatchArgs {
     float lambda;                // in [0, 1]
     float* tgt;                  // workspace [n_rec]: the lambda-return G of every record (bgx_train_lambda.hip)
     float* target_out;           // null, or [n_rec]: a copy of tgt for the caller
+    // zero-sum targets (bgx_td_update_batched, BGX_TDF_ZERO_SUM; needs tgt): the next record's Y and G
+    // enter as 1 - x where the mover (word 11 bit 9) changes; the target stage then runs at every lambda
+    int zero_sum;
 };
 // byte offsets of the workspace's parts (each 16-byte aligned) and its size;
 // tgt follows the TD(0) call's workspace (bytes), bytes_lambda includes it

@@ -23,6 +23,8 @@
 // bgx_tdlambda_update_batched (TrainBatchArgs::tgt set) is the same call with the
 // lambda-return as the target: the target stage of bgx_train_lambda.hip runs
 // between forward and backward, and the backward launch reads tgt[s].
+// bgx_td_update_batched with BGX_TDF_ZERO_SUM (TrainBatchArgs::zero_sum) is that
+// call with the stage's zero-sum instance, at every lambda.
 //
 // Both GEMMs run on the f32-input MFMA (v_mfma_f32_32x32x2_f32: an exact k-ordered
 // fp32 fma chain, so no weight scaling and no dh underflow). A workgroup is 4
@@ -439,8 +441,10 @@ extern "C" hipError_t bgx_launch_td0_batched(const bgx::TrainBatchArgs* args, hi
     hipLaunchKernelGGL(tb_forward_kernel, dim3(a.grid), dim3(TB_T), 0, stream, a);
     // TD(lambda): the target stage, then the backward launch on its targets. lambda = 0
     // keeps the TD(0) backward launch (the same bits by construction); the stage then
-    // runs only to fill target_out
-    const bool lam = a.tgt && a.lambda != 0.0f;
+    // runs only to fill target_out. Zero-sum targets: the inline TD(0) target knows no
+    // movers, so the stage and the backward launch on its targets run at lambda = 0 too
+    if (!a.tgt) a.zero_sum = 0;
+    const bool lam = a.tgt && (a.lambda != 0.0f || a.zero_sum);
     if (lam || (a.tgt && a.target_out)) {
         e = bgx_launch_lambda_targets(&a, stream);
         if (e != hipSuccess) return e;

@@ -5,6 +5,8 @@ episodes (repeated to reach the larger sizes), then per size
   batched_hip   one bgx_td0_update_batched call, event-timed on the stream
   lambda_hip    (--lam L) one bgx_tdlambda_update_batched call on the same
                 records in the same process, event-timed the same way
+  zero_sum_hip  (--lam L --zero-sum) one bgx_td_update_batched call with
+                BGX_TDF_ZERO_SUM, likewise
   sequential    one bgx_td0_update call on the same records, event-timed
   batched_torch DeviceTrainer(batched=True, backend="torch").update_records,
                 wall clock around a synchronize (an eager path: its host work
@@ -85,8 +87,12 @@ def main():
     ap.add_argument("--torch-max-reps", type=int, default=5)
     ap.add_argument("--lam", type=float, default=None,
                     help="also time bgx_tdlambda_update_batched with this lambda beside the TD(0) call")
+    ap.add_argument("--zero-sum", action="store_true",
+                    help="with --lam: also time bgx_td_update_batched with BGX_TDF_ZERO_SUM beside the lambda call")
     args = ap.parse_args()
-    dev = torch.device("cuda")
+    if args.zero_sum and args.lam is None:
+        ap.error("--zero-sum needs --lam")
+    dev =torch.device("cuda")
     torch.manual_seed(0)
     pm, hdr_all, rec_all = harvest(max(args.sizes))
     L = lib()
@@ -129,6 +135,19 @@ def main():
             ms_l = event_ms(batched_lambda, args.reps)
             row["lambda_hip"] = {"lam": args.lam, "ms": ms_l, "episodes_per_s": n_eps / ms_l * 1e3,
                                  "records_per_s": n_rec / ms_l * 1e3, "over_td0": ms_l / ms}
+            if args.zero_sum:
+                # ---- the zero-sum call: the lambda call's launches with the target stage's zero-sum instance
+                p, m, v, step = flat_state(pm, dev)
+
+                def batched_zero_sum():
+                    check(L.bgx_td_update_batched(ptr(rec), ptr(offs), n_eps, n_rec, ptr(p), ptr(m), ptr(v),
+                                                  ptr(step), 1e-3, 0.99, args.lam, 1, 1.0, ptr(met), None, None,
+                                                  ptr(work_l), need_l.value, s))
+
+                ms_z = event_ms(batched_zero_sum, args.reps)
+                row["zero_sum_hip"] = {"lam": args.lam, "ms": ms_z, "episodes_per_s": n_eps / ms_z * 1e3,
+                                       "records_per_s": n_rec / ms_z * 1e3, "over_lambda": ms_z / ms_l,
+                                       "extra_us": (ms_z - ms_l) * 1e3}
         if args.only is None:
             # ---- the sequential kernel (one Adam step per episode)
             p, m, v, step = flat_state(pm, dev)

@@ -3,9 +3,14 @@
 rows 1-3 together): the engine plays, every finished episode's compact
 records feed DeviceTrainer.update_records in the reference's batches of 200
 (--episodes-per-update N for others; --batched --backend hip for the multi-CU update;
---lam L for TD(lambda) targets, with --batched --backend hip or --backend torch),
-and each update's weights go straight back into the engine with the
-reference temperature schedule (ParameterManager.get_temperature)."""
+--lam L for TD(lambda) targets and --zero-sum for targets that take the next
+record from the opponent's side where the mover changes, both with --batched
+--backend hip or --backend torch), and each update's weights go straight back
+into the engine with the reference temperature schedule
+(ParameterManager.get_temperature). --eval-games G then plays the final weights
+against the initial ones (bgx.match.play, 1-ply greedy) and adds games, ppg and
+its standard error to the JSON line; --save PATH writes the final weights as an
+.npz that `python -m bgx.match` reads."""
 import argparse
 import json
 import os
@@ -52,14 +57,20 @@ def main():
                     help="episodes per trainer update (the reference's batch is 200)")
     ap.add_argument("--lam", type=float, default=0.0,
                     help="lambda of the lambda-return targets (0: TD(0), the reference's)")
+    ap.add_argument("--zero-sum", action="store_true",
+                    help="zero-sum targets (DeviceTrainer zero_sum=True): 1 - x of the next record where the mover changes")
+    ap.add_argument("--eval-games", type=int, default=0, metavar="G",
+                    help="after the last update: G games of the final weights against the initial ones, 1-ply greedy")
+    ap.add_argument("--save", default=None, metavar="PATH", help="write the final weights (W1 b1 w2 b2) to this .npz")
     args = ap.parse_args()
     per = args.episodes_per_update
     torch.manual_seed(0)
     pm = LocalPM(BackgammonPolicyNetwork().state_dict())
     trainer = DeviceTrainer(pm, device="cuda", batch_episode_size=per, batched=args.batched, backend=args.backend,
-                            lam=args.lam)
+                            lam=args.lam, zero_sum=args.zero_sum)
     eng = Engine(lanes=args.lanes, seed=0)
     w = dict(zip(("W1", "b1", "w2", "b2"), weights_from(pm.get_parameters())))
+    w_init = {k: np.array(v, copy=True) for k, v in w.items()}
     eng.set_weights(w, pm.get_temperature(), pm.version)
     hdr_buf, rec_buf = [], []
     done, steps, t0, t_train = 0, 0, time.perf_counter(), 0.0
@@ -84,11 +95,20 @@ def main():
             w = dict(zip(("W1", "b1", "w2", "b2"), weights_from(pm.get_parameters())))
             eng.set_weights(w, pm.get_temperature(), pm.version)
     el = time.perf_counter() - t0
+    eng.close()
+    out = {}
+    if args.save:
+        np.savez(args.save, **{k: np.asarray(v) for k, v in w.items()})
+    if args.eval_games > 0:
+        from bgx.match import play
+        res = play(w, w_init, games=args.eval_games, ply=1, greedy=True)
+        out = {"games": res["games"], "ppg": res["ppg"], "ppg_se": res["ppg_se"]}
     print(json.dumps({"updates": done, "episodes_trained": per * done, "env_steps": steps * args.lanes,
                       "wall_s": el, "train_s": t_train, "updates_per_s": done / el,
                       "train_episodes_per_s": per * done / t_train, "train_share": t_train / el, "last_loss": m["loss"],
                       "version": pm.version, "temperature": pm.get_temperature(), "batched": args.batched,
-                      "backend": trainer.backend, "episodes_per_update": per, "lam": trainer.lam}))
+                      "backend": trainer.backend, "episodes_per_update": per, "lam": trainer.lam, "zero_sum": trainer.zero_sum,
+                      **out}))
 
 
 if __name__ == "__main__":
