@@ -33,19 +33,6 @@
 #include "bgx_mlp.h"
 #include "bgx_movegen.h"
 
-#ifndef BGX_FUSED_NW32
-#define BGX_FUSED_NW32 12   // waves per 32-lane workgroup (12: 3 per SIMD at 168 registers; 8: 2 per SIMD at 256; A/B)
-#endif
-#ifndef BGX_FUSED_NW16
-#define BGX_FUSED_NW16 12   // waves per 16-lane workgroup (fewer lanes than 32 x CUs; 8 measured 6 % slower; A/B)
-#endif
-#ifndef BGX_HALF_TICKETS
-#define BGX_HALF_TICKETS 0   // 1: half-lane tickets in a balanced launch's last round (measured slower: DESIGN.md section 9; A/B)
-#endif
-#ifndef BGX_FUSED_LEAF
-#define BGX_FUSED_LEAF 0   // A/B builds: 1 = tier-1 path doubles stream their leaves (run_job<LEAF>)
-#endif
-
 namespace bgx {
 
 constexpr int PROF_STRIDE = 128;   // u64 words per workgroup slot of the development report (f.prof)
@@ -54,12 +41,13 @@ constexpr int PROF_STRIDE = 128;   // u64 words per workgroup slot of the develo
 // fewer lanes than 32 x CUs, else 32 lanes (a step's queue then holds 32 jobs,
 // so the long doubles jobs are spread over more short ones); both on 12 waves
 // (3 per SIMD, 168 registers): the third wave per SIMD hides more of each
-// item's latency than the spills it costs (32 lanes on 8 waves 270 -> 226 M,
-// 16 lanes on 8 waves at 4,096 lanes 216 -> 203 M).
+// item's latency than the spills it costs. (8 waves, 2 per SIMD at 256
+// registers, measured slower: 32 lanes 270 -> 226 M, 16 lanes at 4,096 lanes
+// 216 -> 203 M)
 // LDS: [scratch | W fragments (resident for the launch) | tail | lane values]
 //  scratch = NW tier-1 slices (the pool kernel's layout, bgx_movegen.hip: a
 //  64-word parent map + a region holding the table-mode or the table-free
-//  lists; 4 KB at 8 waves, 3.5 KB at 12), or the workgroup's tier-2 space
+//  lists; 3.5 KB each), or the workgroup's tier-2 space
 template <int FL> struct FusedTail {
     uint4 lut[256];                 // feature LUT (bgx_mlp.h lut_entry)
     float w2s[128];                 // value-head weights
@@ -75,12 +63,11 @@ template <int FL> struct FusedTail {
     LaneState st[FL];               // the lanes' state for the whole launch (written back at the end)
 };
 template <int FL> struct FCfg {
-    static constexpr int NW = FL == 32 ? BGX_FUSED_NW32 : BGX_FUSED_NW16;
+    static constexpr int NW = 12;
     static constexpr int WPE = NW / 4;                   // waves per SIMD
-    // (a 128-slot table with 288-entry frontiers at 12 waves: more tier-2 jobs, not faster)
-    static constexpr int P1_S = 256, P1_F = NW > 8 ? 160 : 224, P1_PF = NW > 8 ? 416 : 480;
+    // (a 128-slot table with 288-entry frontiers: more tier-2 jobs, not faster)
+    static constexpr int P1_S = 256, P1_F = 160, P1_PF = 416;
     static constexpr int SL1 = 64 * 4 + 2 * P1_PF * 4;
-    static_assert(P1_S * 8 + 2 * P1_F * 4 <= 2 * P1_PF * 4, "table layout fits the region");
     static constexpr int F_SCR = NW * SL1 > Slice<S_T2>::bytes ? NW * SL1 : Slice<S_T2>::bytes;
     static constexpr int F_W = F_SCR;
     // tier 2 of a doubles path job: the whole workgroup over the scratch
@@ -120,7 +107,6 @@ __device__ __forceinline__ MovegenArgs job_args(const FusedArgs& f) {
     a.ws_global = f.ws_global;
     a.ws_slots = f.ws_slots;
     a.ws_words_per_wave = f.ws_words_per_block;
-    a.heavy_t = 0x7FFFFFFF;
     a.force_tier = f.force_tier;
     a.err_flags = f.e.err_flags;
     return a;
@@ -132,9 +118,6 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
     constexpr int NW = C::NW, SL1 = C::SL1, F_W = C::F_W, F_TAIL = C::F_TAIL, XS = C::XS;
     constexpr int P1_S = C::P1_S, P1_F = C::P1_F, P1_PF = C::P1_PF;
     constexpr int CP_F = C::CP_F;
-    // the cooperative tier 2 at 12 waves only (at 8 waves, 256 registers, its
-    // registers spill in the step loop: 0 -> 19)
-    constexpr bool COOP2 = NW > 8;
     // two rule-mode non-doubles jobs per wave (FusedArgs::pair) in the 32-lane
     // workgroup only: with 16 lanes on 12 waves a step has about one job per
     // wave, pairing them leaves waves idle, and the code costs the 16-lane
@@ -154,7 +137,6 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
     for (int i = t; i < 64; i += NT) T.tdone[i] = 0u;
     for (int i = t; i < FL; i += NT) T.chosen[i] = T.claim[i] = 0u;
     unsigned qtag = 0u;   // this workgroup's step counter (tags the flags; never 0 on a live step)
-    int half_b = 0;       // thread 0: the half a half-lane ticket steps next (ticket)
     // split-fp16 W fragments, loaded once, global -> LDS by LDS-DMA (every load
     // of a wave in flight at once; the prologue's lane loads overlap them)
     uint4* wl = (uint4*)(lds + F_W);
@@ -179,7 +161,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
     unsigned long long ph[6] = {0, 0, 0, 0, 0, 0}, tc = 0, tw[4] = {0, 0, 0, 0}, t2c = 0, t3n = 0;
     unsigned long long tjd[4] = {0, 0, 0, 0};   // tier-1 job clocks / counts: doubles, non-doubles
     unsigned long long tcs[3] = {0, 0, 0};      // choice: state + Philox refill, pick, env step (lane_advance)
-    unsigned long long tms[3] = {0, 0, 0};      // MLP tile: rows + k mask, MFMA chain issue, drain + epilogue
+    unsigned long long tms[3] = {0, 0, 0};      // MLP tile: rows, MFMA chain issue, drain + epilogue
     // pairing: clocks / count of the non-doubles rule-mode two-move jobs run
     // alone; pipelined claims, those of a rule-mode non-doubles lane, and those
     // of them that saw a second such lane ready and unclaimed; clocks / count
@@ -214,16 +196,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
     // holds the waves' tier-1 slices during the queue.
     const int groups = (launch_args().e.L + FL - 1) / FL;
     uint32_t* const slw = (uint32_t*)(lds + (size_t)w * SL1);   // this wave's tier-1 slice
-    Mem M1;
-    M1.map = slw;
-    M1.tab = (unsigned long long*)(slw + 64);
-    M1.S = P1_S;
-    M1.F = P1_F;
-    M1.fa = slw + 64 + 2 * P1_S;
-    M1.fb = M1.fa + P1_F;
-    M1.pa = slw + 64;
-    M1.pb = M1.pa + P1_PF;
-    M1.PF = P1_PF;
+    Mem M1 = slice_mem<P1_S, P1_F, P1_PF>(slw);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's W fragment loads landed (a barrier follows)
     for (int g = (int)blockIdx.x; g < groups; g += (int)gridDim.x) {
         int nlive, n_iter;
@@ -251,31 +224,16 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
         // budget (thread 0 takes step s + 1's ticket after step s's queue, which
         // expanded the next positions whatever the ticket says: a refused ticket
         // ends the launch with them ready for the next one)
-        // A ticket is the step's lane range, lo | hi << 8 (0: stop). In the
-        // launch's last round (less than one full step of every workgroup left in
-        // the budget) a balanced workgroup steps half its lanes at a time, the two
-        // halves in turn: a half step is ~0.6 of a full one, so the workgroups'
-        // ends, spread over the step that each was in when the budget ran out,
-        // lie closer together. Each lane's game is its own (dice and uniforms are
-        // keyed by lane and its counter), so which lanes step when changes nothing
-        // but how far each lane has got at a harvest.
+        // A ticket is the step's lane range, lo | hi << 8 (0: stop); every
+        // ticket handed out covers all the workgroup's lanes. (Half-lane tickets
+        // in a balanced launch's last round measured slower: DESIGN.md section 9.)
         auto ticket = [&](int s) -> int {
             const FusedArgs& f = launch_args();
             const int full = nlive << 8;
             if (f.budget <= 0) return s < f.n_steps ? full : 0;
             if (s >= f.n_cap) return 0;
-            int lo = 0, hi = nlive;
-            if (BGX_HALF_TICKETS && nlive >= 2) {
-                const long long left =
-                    f.budget - (long long)__hip_atomic_load(f.budget_ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (left < (long long)gridDim.x * (long long)nlive) {
-                    half_b ^= 1;
-                    lo = half_b ? nlive >> 1 : 0;
-                    hi = half_b ? nlive : nlive >> 1;
-                }
-            }
-            const unsigned long long old = atomicAdd(f.budget_ctr, (unsigned long long)(hi - lo));
-            return old < (unsigned long long)f.budget ? lo | (hi << 8) : 0;
+            const unsigned long long old = atomicAdd(f.budget_ctr, (unsigned long long)nlive);
+            return old < (unsigned long long)f.budget ? full : 0;
         };
         // bounded wait for an LDS flag
         auto wait_flag = [&](const unsigned* fl) {
@@ -321,14 +279,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                     FlatCursor fc;
                     auto run_global = [&]() -> int {
                         uint32_t* base = f.ws_global + (size_t)blockIdx.x * f.ws_words_per_block;
-                        Mem G;
-                        const int S = f.ws_slots;
-                        G.tab = (unsigned long long*)base;
-                        G.fa = base + 2 * S;
-                        G.fb = base + 3 * S;
-                        G.map = base + 4 * S;
-                        G.S = S;
-                        G.F = S;
+                        const Mem G = global_mem(base, f.ws_slots);
                         st32<true>(G.map + l, 0u);
                         sync<true>();
                         if (prof) ++t3n;
@@ -337,7 +288,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                         return r < 0 ? 0 : r;
                     };
                     int r2 = -1;
-                    if (COOP2 && in.d0 == in.d1 && doubles_by_path(in.R) && f.force_tier < 3) {
+                    if (in.d0 == in.d1 && doubles_by_path(in.R) && f.force_tier < 3) {
                         auto& C = *(CoopPathLds<NW, CP_F>*)lds;
                         uint32_t* fin = nullptr;
                         r2 = coop_doubles_path<NW, CP_F>(in, C, fin);
@@ -434,14 +385,13 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                             bx = ((const uint4*)src)[0];
                             by = ((const uint4*)src)[1];
                         }
-                        const uint32_t km = tile_kmask(bx, by);
                         unsigned long long i1 = 0, i2 = 0;
                         if (prof) {
                             __builtin_amdgcn_s_waitcnt(0);
                             i1 = wall_clock64();
-                            tms[0] += i1 - i0;   // rows loaded, lane_of, k mask
+                            tms[0] += i1 - i0;   // rows loaded, lane_of
                         }
-                        const float v = mlp_tile4<PROF>(wf, T.lut, T.w2s, k_fs, bx, by, km, &i2);
+                        const float v = mlp_tile4<PROF>(wf, T.lut, T.w2s, k_fs, bx, by, &i2);
                         if (prof) {
                             const float vv = __shfl(v, 0);   // the epilogue's value is ready
                             asm volatile("" ::"v"(vv));
@@ -645,30 +595,22 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                             if (paired) continue;
                             const JobIn in =
                                 make_job(st.w[0], st.w[1], st.w[2], st.w[3], st.w[4], st.w[5], st.w[6], st.p, st.d0, st.d1);
-#if BGX_FUSED_LEAF
-                            // path doubles stream their leaves past the slice's list (no tier 2)
-                            FlatCursor fcj;
-                            const int nf = a.force_tier >= 2 ? -1 : run_job<false, true>(a, g * FL + vq, in, M1, fcj);
-#else
                             int rule2 = 0;
                             uint32_t* fin = nullptr;
                             const int nf = a.force_tier >= 2
                                                ? -1
-                                               : job_records<false>(in, M1, fin, 0x7FFFFFFF, prof ? &rule2 : nullptr);
+                                               : job_records<false>(in, M1, fin, prof ? &rule2 : nullptr);
                             if (nf >= 0) emit_records<false>(a, g * FL + vq, in, fin, nf, 0);
-#endif
                             wave_sync();
                             if (l == 0) T.cnt[vq] = nf;
                             if (prof) {
                                 const int kd = in.d0 == in.d1 ? 0 : 2;
                                 tjd[kd] += wall_clock64() - q1;
                                 tjd[kd + 1] += 1;
-#if !BGX_FUSED_LEAF
                                 if (rule2) {
                                     tpr[0] += wall_clock64() - q1;
                                     tpr[1] += 1;
                                 }
-#endif
                             }
                         }
                     }

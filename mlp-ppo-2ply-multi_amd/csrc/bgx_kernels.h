@@ -50,7 +50,6 @@ struct MovegenArgs {
     int ws_slots;                // power of two
     size_t ws_words_per_wave;    // >= 5 * ws_slots
     int ovf_zeroed;              // caller zeroed *ovf_count on the stream already (skip the memset)
-    int heavy_t;                 // set by the launcher: doubles level size handed to the block tier
     int force_table;             // test hook (BGX_MG_TEST_TABLE=1): every job takes the hash-table path
                                  //   (no table-free doubles / non-doubles rules), as a cross-check
     int force_tier;              // test hook (BGX_MG_TEST_TIER): 2/3 = skip the LDS tiers below

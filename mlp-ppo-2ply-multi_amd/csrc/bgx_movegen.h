@@ -40,13 +40,16 @@ constexpr unsigned long long EMPTY64 = ~0ull;
 constexpr uint32_t KEY_EMPTY4 = 0xFFFFFu;   // four empty 5-bit fields
 constexpr uint32_t KEYMASK = 0xFFFFFu;
 constexpr uint32_t FLAG1 = 0x80000000u;      // "parent had exactly one move"
-// LDS slices: tier 1 runs every job in SLICE_T1 bytes (512-slot table + two
-// 512-entry frontiers = 8 KB, 20 waves per CU); a job whose level outgrows it
-// is re-run by tier 2 in a 32 KB slice (2048 slots), and what still overflows
-// by the global-memory kernel. Results are identical in every tier.
-// slice = table [S] u64 | fa [S - 32] u32 | fb [S - 32] u32 | map [64] u32
+// LDS slices: tier 1 runs every job in its wave's slice, a 64-word parent map
+// and a region that holds either a 256-slot table with two frontiers or the
+// two lists of the table-free modes (slice_mem below): 4 KB per wave in the
+// movegen kernels (224-entry frontiers, 480-entry lists: bgx_movegen.hip),
+// 3.5 KB in the fused step (160 / 416: bgx_fused.hip). A job whose level
+// outgrows it is re-run by tier 2 in a 32 KB slice (S_T2 = 2048 slots, lds_mem
+// below), and what still overflows on a global-memory workspace (global_mem).
+// Results are identical in every tier.
+// tier-2 slice = table [S] u64 | fa [S - 32] u32 | fb [S - 32] u32 | map [64] u32
 template <int S> struct Slice { static constexpr int F = S - 32, bytes = S * 8 + 2 * F * 4 + 64 * 4; };
-constexpr int S_T1 = 512;
 constexpr int S_T2 = 2048;
 
 struct Mem {
@@ -770,13 +773,11 @@ BGX_DEV bool expand_keep(const Mem& M, const Moves& pm, int c, KeyFn kfn, uint32
 }
 
 // ------------------------------------------------------------------ the job
-// returns the record count, or -1 when the slice overflowed (fallback)
-// heavy_t: a doubles level with more children than this returns -2 (the
-// small-launch kernel then expands the job with the whole block)
+// returns the record count, or -1 when the slice overflowed
 // rule2 (or null; the fused development report): set to 1 when the job took
 // the non-doubles rule-mode two-move branch
 template <bool G>
-BGX_DEV int job_records(const JobIn& in, const Mem& M, uint32_t*& fin_out, int heavy_t, int* rule2 = nullptr) {
+BGX_DEV int job_records(const JobIn& in, const Mem& M, uint32_t*& fin_out, int* rule2 = nullptr) {
     STAMP_BEGIN;
     const Root& R = in.R;
     const int l = lane_id();
@@ -947,7 +948,6 @@ BGX_DEV int job_records(const JobIn& in, const Mem& M, uint32_t*& fin_out, int h
                     }
                     nn += Tc;
                     T += (uint32_t)Tc;
-                    if ((int)T > heavy_t) return -2;
                 }
                 sync<G>();
                 if (T == 0) break;
@@ -1000,7 +1000,6 @@ BGX_DEV int job_records(const JobIn& in, const Mem& M, uint32_t*& fin_out, int h
                     return -1;
                 }
                 T += tot;
-                if ((int)T > heavy_t) return -2;
             }
             if (T == 0) break;
             uint32_t* t = fa; fa = fb; fb = t;
@@ -1489,13 +1488,12 @@ BGX_DEV uint32_t board_dbl_emit(const MovegenArgs& a, int j0, const JobIn& in, c
 // the slice (path_doubles_emit); the large launches (pool / reply kernels) use
 // it, the fused 1-ply kernel keeps job_records (its registers are at the cap)
 template <bool G, bool LEAF = false>
-BGX_DEV int run_job(const MovegenArgs& a, int j, const JobIn& in, const Mem& M, FlatCursor& fc,
-                    int heavy_t = 0x7FFFFFFF) {
+BGX_DEV int run_job(const MovegenArgs& a, int j, const JobIn& in, const Mem& M, FlatCursor& fc) {
     if constexpr (LEAF) {
         if (in.d0 == in.d1 && doubles_by_path(in.R) && !M.force_table) return path_doubles_emit<G>(a, j, in, M, fc);
     }
     uint32_t* fin = nullptr;
-    const int nfin = job_records<G>(in, M, fin, heavy_t);
+    const int nfin = job_records<G>(in, M, fin);
     if (nfin < 0) return nfin;
     const int base = begin_emit(a, j, nfin, fc);
     if (base >= 0) emit_records<G>(a, j, in, fin, nfin, base);
@@ -1513,8 +1511,18 @@ BGX_DEV int run_job(const MovegenArgs& a, int j, const JobIn& in, const Mem& M, 
 //    order a roll's pass-0 parents precede its pass-1 parents -- the
 //    reference's (pass, i, j) enumeration (handle_non_doubles,
 //    generate_all_moves.py:23-68);
-//  * a roll's children are expanded flat over its parent lanes (64 per
-//    round, flat_parent) and its records appended to one list for the root;
+//  * all 15 rolls' children are expanded as ONE flat sequence (roll-major,
+//    then parent lane, then move) cut into 64-child rounds, not one round trip
+//    per roll: a roll has ~40 children, so per-roll rounds ran half empty and
+//    the 15 dependent scan / parent-map / shuffle chains of a root were its
+//    latency. Each lane is a parent in the 5 rolls that pair its die with
+//    another; its children lists (m2, after the rule-mode pass-1 restriction)
+//    go to an LDS table [lane][partner die] and its first move to pinfo[lane];
+//    a child finds its parent through the 64-word map (marks = start << 10 |
+//    roll << 6 | lane, + 1; a max-scan carries the latest start) and reads the
+//    two LDS words, so no shuffle is needed. Singles rolls (no 2-move play)
+//    give each eligible parent one child: the single itself. The records are
+//    appended to one list for the root;
 //  * the root's records are written in one pass (all 64 lanes busy), and the
 //    15 jobs get their offsets inside that block.
 // Roots it applies to (the others return -1 and run as per-roll jobs):
@@ -1535,147 +1543,11 @@ BGX_DEV int run_job(const MovegenArgs& a, int j, const JobIn& in, const Mem& M, 
 // rolls in DICE_ROLLS order (two_ply.py:10-32) without the doubles; lane q of
 // `rcnt` = the record count of the q-th non-doubles roll. Returns the record
 // count, or -1 (not applicable, more than 64 first moves, or the list is full).
+// aux: >= 64 * 7 + 16 words of LDS (the slice's second list).
 constexpr int ND_ROLLS = 15;
 
 template <int LISTCAP>
-BGX_DEV int board_nd_records(const Root& R, uint32_t* map, uint32_t* list, int& rcnt) {
-    const int l = lane_id();
-    const bool p0 = R.player == 0;
-    const bool onbar = R.bar > 0u;
-    const bool rule = !onbar && nd_by_rule(R);
-    rcnt = 0;
-    if (!onbar && !rule) return -1;
-    const uint32_t occ = occ24(R.m0, R.m1, R.m2);
-    auto entry = [&](int d) -> int { return p0 ? d - 1 : 24 - d; };
-    auto open = [&](int d) -> bool { return !((R.block >> entry(d)) & 1u); };
-    // first moves per die (wave-uniform): die d owns lanes [st(d), st(d) + n(d)),
-    // dice descending; the lane's die is the lowest d with st(d) <= lane
-    int st = 0, dl = 6, kst = 0;
-    uint32_t srcl = 0u;
-#pragma unroll
-    for (int d = 6; d >= 1; --d) {
-        const uint32_t sd = rule ? occ & ok_mask(R.block, d, R.player) : (open(d) ? 1u : 0u);
-        if (l >= st) {
-            dl = d;
-            srcl = sd;
-            kst = st;
-        }
-        st += __popc(sd);
-    }
-    const int nf = st;
-    if (nf > 64) return -1;
-    const bool valid = l < nf;
-    // the lane's first move: source s1 (24 = the bar), destination t1, hit h1,
-    // and the occupancy of the board after it (the child's normal-move sources)
-    int s1 = 24, t1 = 0;
-    uint32_t base2 = 0u;
-    if (valid) {
-        if (rule) {
-            s1 = select_bit_fast(srcl, l - kst);
-            t1 = p0 ? s1 + dl : s1 - dl;
-            const uint32_t last1 = nib(R.m0, R.m1, R.m2, s1) == 1u ? 1u << s1 : 0u;
-            base2 = (occ & ~last1) | (1u << t1);
-        } else {
-            t1 = entry(dl);
-            base2 = occ | (1u << t1);
-        }
-    }
-    const bool h1 = valid && ((R.blot >> t1) & 1u);
-    const uint32_t pinfo = (uint32_t)s1 | ((uint32_t)t1 << 5) | (h1 ? 1u << 10 : 0u);
-    const bool child_bar = R.bar >= 2u;   // after one entry the mover is still on the bar
-    int total = 0, q = 0;
-    for (int Ld = 1; Ld <= 5; ++Ld) {
-        for (int Hd = Ld + 1; Hd <= 6; ++Hd, ++q) {
-            const bool isH = valid && dl == Hd, isL = valid && dl == Ld;
-            const uint32_t okH = ok_mask(R.block, Hd, R.player), okL = ok_mask(R.block, Ld, R.player);
-            uint32_t m2 = 0u;
-            if (isH || isL) {
-                if (child_bar) m2 = open(isH ? Ld : Hd) ? 1u << 24 : 0u;   // bit 24: the bar entry
-                else m2 = base2 & (isH ? okL : okH);
-            }
-            const bool two1 = ballot(isH && m2 != 0u) != 0ull;
-            const bool two2 = ballot(isL && m2 != 0u) != 0ull;
-            const int nH = rule ? __popc(occ & okH) : (open(Hd) ? 1 : 0);
-            int cq = 0;
-            if (two1 || (nH != 1 && two2)) {
-                // 2-move records
-                if (rule && isL) {   // a pass-1 parent adds only its chain or reverse-chain child
-                    const int rv = p0 ? s1 - Hd : s1 + Hd;
-                    m2 &= (1u << t1) | ((rv >= 0 && rv < 24) ? 1u << rv : 0u);
-                }
-                // bar mode: the pass-0 play that a pass-1 play can repeat (see above)
-                uint32_t K0 = ND_DROP;
-                if (!rule) {
-                    const int eH = entry(Hd), eL = entry(Ld);
-                    const bool hH = (R.blot >> eH) & 1u;
-                    if (child_bar) {
-                        if (open(Hd) && open(Ld))
-                            K0 = nd_key(24u, (uint32_t)eH, hH, 24u, (uint32_t)eL, ((R.blot >> eL) & 1u) != 0u);
-                    } else if (open(Hd) && ((okL >> eH) & 1u)) {
-                        const int t2 = p0 ? eH + Ld : eH - Ld;
-                        const uint32_t b2 = R.blot & ~(hH ? 1u << eH : 0u);
-                        K0 = nd_key(24u, (uint32_t)eH, hH, (uint32_t)eH, (uint32_t)t2, ((b2 >> t2) & 1u) != 0u);
-                    }
-                }
-                const int c = __popc(m2);
-                const int incl = wave_incl_scan(c);
-                const int excl = incl - c;
-                const int T = lane63(incl);
-                const uint32_t pi = pinfo | (isL ? 1u << 11 : 0u);
-                for (int b = 0; b < T; b += 64) {
-                    const int r = b + l;
-                    const int p = flat_parent<false>(map, excl, c, b);
-                    const int j = r - __shfl(excl, p, 64);
-                    const uint32_t src2 = (uint32_t)__shfl((int)m2, p, 64);
-                    const uint32_t ppi = (uint32_t)__shfl((int)pi, p, 64);
-                    const uint32_t ps1 = ppi & 31u, pt1 = (ppi >> 5) & 31u;
-                    const bool ph1 = (ppi >> 10) & 1u;
-                    const int pp = (int)((ppi >> 11) & 1u);
-                    const int s2 = (src2 >> 24) ? 24 : select_bit_fast(src2, j);
-                    const int t2 = dest_of(R, s2, pp ? Hd : Ld);
-                    const uint32_t blot2 = R.blot & ~(ph1 ? 1u << pt1 : 0u);
-                    const bool h2 = t2 < 24 && ((blot2 >> t2) & 1u);
-                    const uint32_t key = nd_key(ps1, pt1, ph1, (uint32_t)s2, (uint32_t)t2, h2);
-                    const bool keep = rule ? nd_first(R, occ, pp, (int)ps1, (int)pt1, s2, t2, Hd, Ld)
-                                           : !(pp == 1 && key == K0);
-                    const bool sv = r < T && keep;
-                    const uint64_t bm = ballot(sv);
-                    const int ns = __popcll(bm);
-                    if (total + cq + ns > LISTCAP) return -1;
-                    if (sv) list[total + cq + mask_prefix(bm)] = key;
-                    cq += ns;
-                }
-            } else {
-                // singles: high-die singles, then low-die singles unless the high
-                // die has exactly one move (handle_non_doubles 70-81; the pass-2 skip)
-                const bool sv = isH || (isL && nH != 1);
-                const uint64_t bm = ballot(sv);
-                cq = __popcll(bm);
-                if (total + cq > LISTCAP) return -1;
-                if (sv) list[total + mask_prefix(bm)] = nd_key((uint32_t)s1, (uint32_t)t1, h1, 31u, 31u, false);
-            }
-            rcnt = l == q ? cq : rcnt;
-            total += cq;
-        }
-    }
-    wave_sync();
-    return total;
-}
-
-// The same records, all 15 rolls' children as ONE flat sequence (roll-major,
-// then parent lane, then move) cut into 64-child rounds, instead of one round
-// trip per roll: a roll has ~40 children, so per-roll rounds ran half empty
-// and the 15 dependent scan / parent-map / shuffle chains of a root were its
-// latency. Each lane is a parent in the 5 rolls that pair its die with
-// another; its children lists (m2, after the rule-mode pass-1 restriction) go
-// to an LDS table [lane][partner die] and its first move to pinfo[lane]; a
-// child finds its parent through the 64-word map (marks = start << 10 |
-// roll << 6 | lane, + 1; a max-scan carries the latest start) and reads the
-// two LDS words, so no shuffle is needed. Singles rolls (no 2-move play) give
-// each eligible parent one child: the single itself. aux: >= 64 * 7 + 16
-// words of LDS (the slice's second list).
-template <int LISTCAP>
-BGX_DEV int board_nd_records2(const Root& R, uint32_t* map, uint32_t* list, uint32_t* aux, int& rcnt) {
+BGX_DEV int board_nd_records(const Root& R, uint32_t* map, uint32_t* list, uint32_t* aux, int& rcnt) {
     const int l = lane_id();
     const bool p0 = R.player == 0;
     const bool onbar = R.bar > 0u;
@@ -1835,7 +1707,7 @@ BGX_DEV int board_nd_records2(const Root& R, uint32_t* map, uint32_t* list, uint
             if (rule) {
                 keep = nd_first(R, occ, pp, (int)ps1, (int)pt1, s2, t2, H, L);
             } else if (pp == 1) {
-                keep = key != k0tab[qq];   // bar mode (board_nd_records)
+                keep = key != k0tab[qq];   // bar mode (see the comment above the function)
             }
         }
         const bool sv = r < total && keep;
@@ -2147,6 +2019,38 @@ BGX_DEV Mem lds_mem(unsigned long long* smem) {
     M.map[lane_id()] = 0u;
     wave_sync();
     return M;
+}
+
+// A wave's tier-1 slice at sl: map [64] u32, then a region that is either the
+// table-mode layout (table [S] u64 | fa [F] | fb [F]) or, laid over it, the
+// table-free modes' two lists (pa [PF] | pb [PF]). The caller zeroes the map.
+template <int S, int F, int PF>
+BGX_DEV Mem slice_mem(uint32_t* sl) {
+    static_assert(S * 8 + 2 * F * 4 <= 2 * PF * 4, "table layout fits the region");
+    Mem M;
+    M.map = sl;
+    M.tab = (unsigned long long*)(sl + 64);
+    M.S = S;
+    M.F = F;
+    M.fa = sl + 64 + 2 * S;
+    M.fb = M.fa + F;
+    M.pa = sl + 64;
+    M.pb = M.pa + PF;
+    M.PF = PF;
+    return M;
+}
+
+// Tier 3: a block's global-memory workspace at base, table [S] u64 | fa [S] |
+// fb [S] | map [64]. The caller zeroes the map (st32<true>, sync<true>).
+BGX_DEV Mem global_mem(uint32_t* base, int S) {
+    Mem G;
+    G.tab = (unsigned long long*)base;
+    G.fa = base + 2 * S;
+    G.fb = base + 3 * S;
+    G.map = base + 4 * S;
+    G.S = S;
+    G.F = S;
+    return G;
 }
 
 BGX_DEV void push_ovf(const MovegenArgs& a, int j) {

@@ -7,8 +7,10 @@
 //
 // One job = one (board, player, dice); one wavefront per job (64-thread
 // workgroups, persistent grid-stride over jobs); all job state lives in an
-// LDS slice: a hash table of 64-bit {key, ordinal} words and two frontier
-// lists (8 KB in tier 1, see Slice below).
+// LDS slice: a 64-word parent map and a hash table of 64-bit {key, ordinal}
+// words with two frontier lists, or, for the jobs that need no table (doubles
+// by path, non-doubles by rule: most), two lists laid over the table (4 KB
+// per wave in tier 1: slice_mem, bgx_movegen.h).
 //
 // The reference's DFS emits the DISTINCT resulting boards in first-reach
 // (lexicographic path) order and keeps the maximal-length plays. Here:
@@ -45,42 +47,29 @@ namespace bgx {
 // Slice (4 KB per wave): a 64-word parent map, then a region that is either
 // the table-mode layout (256-slot table + two 224-entry frontiers) or, for the
 // table-free modes (doubles by path, non-doubles by rule: most jobs), two
-// 480-entry lists laid over it. With half the round-1 8 KB slice the pool is
+// 480-entry lists laid over it. At 4 KB (round 1 had 8 KB slices) the pool is
 // bound by registers, not LDS: 16-wave workgroups, two per CU, at <= 64 VGPRs
 // = 8 waves per SIMD, the hardware maximum (amdgpu_waves_per_eu). Measured on
 // the 2-ply K=4 reply launch at 8,192 lanes (profiles/r2/ab_pool): 8 KB slices
 // / 5 waves per SIMD 0.64 ms, 4 KB / 7 waves 0.54 ms, 4 KB / 8 waves 0.475 ms.
-#ifndef BGX_REPLY_LEAF
-#define BGX_REPLY_LEAF 1   // A/B builds: 0 = path doubles never stream their leaves (job_records)
-#endif
 #ifndef BGX_REPLY_SUBQ
 #define BGX_REPLY_SUBQ 1   // A/B builds: 0 = an uncovered root's 15 jobs run on its own wave
 #endif
-#ifndef BGX_BND
-#define BGX_BND 2          // 1 = the per-roll-round board_nd_records (A/B builds)
-#endif
-#ifndef BGX_REPLY_DBL_TAIL
-#define BGX_REPLY_DBL_TAIL 4   // board-major doubles launch: 64ths of the rows left in per-roll items
-#endif
-#ifndef BGX_REPLY_WG
-#define BGX_REPLY_WG 1   // A/B builds: 0 = the reply launch's waves reserve rows in per-wave chunks
-#endif
-#ifndef BGX_POOL_WPE
-#define BGX_POOL_WPE 8
-#endif
+// board-major doubles launch: 64ths of the rows left in per-roll items (the
+// default of the environment knob of the same name)
+constexpr int BGX_REPLY_DBL_TAIL = 4;
 constexpr int PW = 16;                                   // waves per workgroup (two per CU)
 constexpr int P_S = 256;                                 // table slots (table mode)
 constexpr int P_F = 224;                                 // table-mode frontier entries
 constexpr int P_PF = 480;                                // table-free list entries
 constexpr int PSL = 64 * 4 + 2 * P_PF * 4;               // slice bytes (4 KB)
-static_assert(P_S * 8 + 2 * P_F * 4 <= 2 * P_PF * 4, "table layout fits the region");
 static_assert(PW * PSL + 16 <= 80 * 1024, "two workgroups per CU");
 
 // IN / OUT >= 0: the input / output mode is fixed at compile time (the 2-ply
 // reply launch: IN_TWOPLY, OUT_PACKED_FLAT), so the other modes' code and
 // arguments are dead (fewer live scalar registers); -1: read from the arguments
 template <int IN, int OUT>
-__global__ __launch_bounds__(64 * PW) __attribute__((amdgpu_waves_per_eu(BGX_POOL_WPE))) void movegen_pool_kernel(
+__global__ __launch_bounds__(64 * PW) __attribute__((amdgpu_waves_per_eu(8))) void movegen_pool_kernel(
     MovegenArgs a0) {
     MovegenArgs a = a0;
     if constexpr (IN >= 0) a.in_mode = IN;
@@ -89,16 +78,7 @@ __global__ __launch_bounds__(64 * PW) __attribute__((amdgpu_waves_per_eu(BGX_POO
     __shared__ int next_job;
     const int w = (int)threadIdx.x >> 6, l = lane_id();
     uint32_t* sl = (uint32_t*)(smem + (size_t)w * (PSL / 8));
-    Mem M;
-    M.map = sl;
-    M.tab = (unsigned long long*)(sl + 64);
-    M.S = P_S;
-    M.F = P_F;
-    M.fa = sl + 64 + 2 * P_S;
-    M.fb = M.fa + P_F;
-    M.pa = sl + 64;
-    M.pb = M.pa + P_PF;
-    M.PF = P_PF;
+    Mem M = slice_mem<P_S, P_F, P_PF>(sl);
     M.force_table = a.force_table;
     M.map[l] = 0u;
     const int n_jobs = uniform(job_count(a));
@@ -124,7 +104,7 @@ __global__ __launch_bounds__(64 * PW) __attribute__((amdgpu_waves_per_eu(BGX_POO
         if (in.skip) {
             begin_emit(a, j, 0, fc);
         } else {
-            const int r = a.force_tier >= 2 ? -1 : run_job<false, BGX_REPLY_LEAF != 0>(a, j, in, M, fc, a.heavy_t);
+            const int r = a.force_tier >= 2 ? -1 : run_job<false, true>(a, j, in, M, fc);
             if (r < 0 && l == 0) push_ovf(a, j);
         }
         k = kn;
@@ -148,7 +128,7 @@ __global__ __launch_bounds__(64 * PW) __attribute__((amdgpu_waves_per_eu(BGX_POO
 // together. Not DBL: every row in per-roll items.
 constexpr int REPLY_SUBQ = 1024;   // sub-queue entries per workgroup (4 KB of LDS: 2 x 68 KB per CU)
 template <bool DBL>
-__global__ __launch_bounds__(64 * PW) __attribute__((amdgpu_waves_per_eu(BGX_POOL_WPE))) void movegen_reply_kernel(
+__global__ __launch_bounds__(64 * PW) __attribute__((amdgpu_waves_per_eu(8))) void movegen_reply_kernel(
     MovegenArgs a0) {
     MovegenArgs a = a0;
     a.in_mode = IN_TWOPLY;
@@ -159,16 +139,7 @@ __global__ __launch_bounds__(64 * PW) __attribute__((amdgpu_waves_per_eu(BGX_POO
     int& items_done = wgr.done;
     const int w = (int)threadIdx.x >> 6, l = lane_id();
     uint32_t* sl = (uint32_t*)(smem + (size_t)w * (PSL / 8));
-    Mem M;
-    M.map = sl;
-    M.tab = (unsigned long long*)(sl + 64);
-    M.S = P_S;
-    M.F = P_F;
-    M.fa = sl + 64 + 2 * P_S;
-    M.fb = M.fa + P_F;
-    M.pa = sl + 64;
-    M.pb = M.pa + P_PF;
-    M.PF = P_PF;
+    Mem M = slice_mem<P_S, P_F, P_PF>(sl);
     M.force_table = a.force_table;
     M.map[l] = 0u;
     const int n_jobs = uniform(job_count(a));
@@ -213,7 +184,7 @@ __global__ __launch_bounds__(64 * PW) __attribute__((amdgpu_waves_per_eu(BGX_POO
     }
     __syncthreads();
     FlatCursor fc;
-    if (BGX_REPLY_WG) fc.wg = &wgr;
+    fc.wg = &wgr;
     int k = w;
     RawJob raw;
     if (k < nk) {
@@ -227,7 +198,7 @@ __global__ __launch_bounds__(64 * PW) __attribute__((amdgpu_waves_per_eu(BGX_POO
         if (in.skip) {
             begin_emit(a, j, 0, fc);
         } else {
-            const int r = a.force_tier >= 2 ? -1 : run_job<false, BGX_REPLY_LEAF != 0>(a, j, in, M, fc, a.heavy_t);
+            const int r = a.force_tier >= 2 ? -1 : run_job<false, true>(a, j, in, M, fc);
             if (r < 0 && l == 0) push_ovf(a, j);
         }
     };
@@ -345,8 +316,7 @@ __global__ __launch_bounds__(64 * PW) __attribute__((amdgpu_waves_per_eu(BGX_POO
             const JobIn in = decode_job(a, j0 + 1, cur);   // the row's root (the dice are not used)
             int n = -1, rc = 0;
             if (!in.skip && !a.force_table && a.force_tier < 2 && j0 + 21 <= n_jobs && !(a.reply_groups & 0x100))
-                n = BGX_BND == 2 ? board_nd_records2<P_PF>(in.R, M.map, M.pa, M.pb, rc)
-                                 : board_nd_records<P_PF>(in.R, M.map, M.pa, rc);
+                n = board_nd_records<P_PF>(in.R, M.map, M.pa, M.pb, rc);
             if (n < 0 && (a.reply_groups & 0x80)) n = -2;   // tools hook: leave uncovered roots out
             if (n >= 0) {
                 // the row's records in one block; job q's records at its prefix
@@ -373,6 +343,10 @@ __global__ __launch_bounds__(64 * PW) __attribute__((amdgpu_waves_per_eu(BGX_POO
                 // sub-queue when it has room, else run here. (A balanced pool launch
                 // over all such jobs measured slower: its chunk reservations left
                 // 12 % more gap rows for the reply MLP, profiles/round4/reply/.)
+                // Written out here, not through share() below: with share()
+                // instantiated at both sites MovegenArgs stayed in scratch (a 540 B
+                // frame) and that build faulted on the GPU (DESIGN.md section 4,
+                // "The round-4 fault, narrowed").
                 int slot = -1;
                 if (BGX_REPLY_SUBQ && l == 0 && j0 + 21 <= n_jobs) {
                     int r = lds_ld(&sub_res);
@@ -424,16 +398,7 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(8))) void m
     const int w = (int)threadIdx.x >> 6, l = lane_id();
     const int n_jobs = uniform(job_count(a));
     uint32_t* sl = (uint32_t*)(smem + (size_t)w * (PSL / 8));
-    Mem M;
-    M.map = sl;
-    M.tab = (unsigned long long*)(sl + 64);
-    M.S = P_S;
-    M.F = P_F;
-    M.fa = sl + 64 + 2 * P_S;
-    M.fb = M.fa + P_F;
-    M.pa = sl + 64;
-    M.pb = M.pa + P_PF;
-    M.PF = P_PF;
+    Mem M = slice_mem<P_S, P_F, P_PF>(sl);
     M.force_table = a.force_table;
     M.map[l] = 0u;
     for (int win = (int)blockIdx.x; win * BW < n_jobs; win += (int)gridDim.x) {
@@ -447,9 +412,9 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(8))) void m
             if (in.skip) {
                 emit = true;
             } else {
-                const int r = a.force_tier >= 2 ? -1 : job_records<false>(in, M, fin, a.heavy_t);
+                const int r = a.force_tier >= 2 ? -1 : job_records<false>(in, M, fin);
                 if (r < 0) {
-                    if (l == 0) push_ovf(a, j);   // overflow or heavy doubles: tier 2 owns the job
+                    if (l == 0) push_ovf(a, j);   // overflow: tier 2 owns the job
                 } else {
                     emit = true;
                     nf = r;
@@ -507,14 +472,7 @@ __global__ __launch_bounds__(NTH) void movegen_block_kernel(MovegenArgs a) {
     // tier 3, wave 0 only
     auto run_global = [&](int j, const JobIn& in) {
         uint32_t* base = a.ws_global + (size_t)blockIdx.x * a.ws_words_per_wave;
-        Mem G;
-        const int S = a.ws_slots;
-        G.tab = (unsigned long long*)base;
-        G.fa = base + 2 * S;
-        G.fb = base + 3 * S;
-        G.map = base + 4 * S;
-        G.S = S;
-        G.F = S;
+        Mem G = global_mem(base, a.ws_slots);
         G.force_table = a.force_table;
         st32<true>(G.map + l, 0u);
         sync<true>();
@@ -600,9 +558,6 @@ extern "C" hipError_t bgx_launch_movegen(const bgx::MovegenArgs* args, hipStream
     a.force_table = test_table;
     ev = getenv("BGX_REPLY_GROUPS");
     a.reply_groups = ev ? (int)strtol(ev, nullptr, 0) : 0;
-    // doubles run table-free in tier 1 (the block-cooperative hand-off of heavy
-    // doubles measured slower since then: DESIGN.md §4)
-    a.heavy_t = 0x7FFFFFFF;
     // latency-bound launches (at most 4 windows of 16 jobs per CU, host-known
     // count): tier 1 in 16-wave blocks with one flat-row atomic per block;
     // larger launches: the balanced pool kernel
@@ -636,7 +591,7 @@ extern "C" hipError_t bgx_launch_movegen(const bgx::MovegenArgs* args, hipStream
             ev = getenv("BGX_REPLY_DBL");
             const bool dbl = !ev || atoi(ev) != 0;
             ev = getenv("BGX_REPLY_DBL_TAIL");
-            a.dbl_tail64 = ev ? atoi(ev) : BGX_REPLY_DBL_TAIL;
+            a.dbl_tail64 = ev ? atoi(ev) : bgx::BGX_REPLY_DBL_TAIL;
             int rb = n_cu * per_cup;
             const int need_r = ((a.n_jobs + 20) / 21 * 7 + bgx::PW - 1) / bgx::PW;   // at most 7 items per row
             if (!a.n_jobs_dev && need_r < rb) rb = need_r;

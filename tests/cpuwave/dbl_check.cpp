@@ -56,7 +56,6 @@ void setup_args(Out& o, int cap) {
     a.job_off = o.off;
     a.job_cnt = o.cnt;
     a.err_flags = &o.err;
-    a.heavy_t = 0x7FFFFFFF;
 }
 
 // a random position: the mover's 15 checkers (bar / off / points), the
@@ -156,13 +155,13 @@ int main(int argc, char** argv) {
             // same slice (it must leave the parent map zero)
             {
                 int rc = 0;
-                const int n_nd = board_nd_records2<P_PF>(in[1].R, S.M.map, S.M.pa, S.M.pb, rc);
+                const int n_nd = board_nd_records<P_PF>(in[1].R, S.M.map, S.M.pa, S.M.pb, rc);
                 (void)n_nd;
                 emu::sync();
                 if (lane == 0)
                     for (int q = 0; q < 64; ++q)
                         if (S.slice[q]) {
-                            printf("root %d: board_nd_records2 left map[%d] = %u (n %d)\n", i, q, S.slice[q], n_nd);
+                            printf("root %d: board_nd_records left map[%d] = %u (n %d)\n", i, q, S.slice[q], n_nd);
                             ++bad;
                             break;
                         }

@@ -56,7 +56,6 @@ void set_out(Out& o) {
     S.a.out_mode = OUT_PACKED_SLOT;
     S.a.cap = CAP;
     S.a.out_packed = o.rows.data();
-    S.a.heavy_t = 0x7FFFFFFF;
 }
 }  // namespace
 
@@ -122,7 +121,7 @@ int main(int argc, char** argv) {
             emu::sync();
             uint32_t* fin = nullptr;
             int rule2 = 0;
-            const int nf = job_records<false>(in, S.M, fin, 0x7FFFFFFF, &rule2);
+            const int nf = job_records<false>(in, S.M, fin, &rule2);
             if (nf >= 0) emit_records<false>(S.a, JA, in, fin, nf, 0);
             emu::sync();
             if (lane == 0) {

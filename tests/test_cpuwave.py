@@ -10,7 +10,7 @@ test_board_major_doubles_equals_per_roll: the board-major doubles item
 bgx_movegen.h) gives every (root, die) the records of the per-roll path
 (run_job: path_doubles_emit / job_records, which the GPU reply tests check
 against the oracle), in the same order, written only inside the job's
-reserved rows; the non-doubles item (board_nd_records2) runs first on the same
+reserved rows; the non-doubles item (board_nd_records) runs first on the same
 slice and must leave the parent map zero. Random positions (bar 0-2, borne-off
 checkers). The 3,650 positions of tests/test_gpu_reply.py passed the same
 check (tools: `dbl_check 4000 1 positions.bin`, ~9 min).

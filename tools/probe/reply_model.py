@@ -212,7 +212,7 @@ if __name__ == "__main__":
 
 
 def board_nd_v2(R):
-    """The flat-round form (board_nd_records2): counts per (lane, partner die),
+    """The flat-round form (board_nd_records as the kernel runs it): counts per (lane, partner die),
     roll-major flat starts, 64-child rounds with marks + max-scan + carry.
     Same {(L, H): keys} as board_nd, or None."""
     onbar = R.bar > 0
