@@ -53,34 +53,54 @@ struct LaneRng {
     BGX_DEV void skip_uniform() { if (!dt.tab) ++ctr; }
 };
 
-// The same stream drawn by a half-wave (two game lanes per wavefront, one
-// per half): lane k of the half evaluates counter base + k, draws come over
-// by shuffles within the half.
-struct HalfRng {
-    uint64_t key, ctr, base;
-    u32x4 batch;
+// The same stream with a step's draws made ahead (the fused 1-ply kernel: one
+// wave draws for all of its workgroup's lanes, bgx_fused.hip). A lane's step
+// consumes the draw at its counter c (the sampling uniform, or the roll of a
+// pass) and the one at c + 1 (the roll after a move); the slot holds what
+// they give: the raw .x word at c and both counters' dice, each pair packed
+// a | b << 3 in a half-word (d[k]: counter c + k). 8 bytes per lane.
+struct DrawSlot {
+    uint32_t x;
+    uint16_t d[2];
+};
+static_assert(sizeof(DrawSlot) == 8, "8 bytes per lane");
+BGX_DEV uint32_t dice_pack(int a, int b) { return (uint32_t)a | ((uint32_t)b << 3); }
+BGX_DEV void dice_unpack(uint32_t p, int& a, int& b) {
+    a = (int)(p & 7u);
+    b = (int)((p >> 3) & 7u);
+}
+// one thread's share of a slot: the draw at counter c + k (k = 0, 1) of global lane gid
+BGX_DEV void draw_fill(DrawSlot& s, uint64_t seed, uint32_t gid, uint64_t c, int k) {
+    const u32x4 r = philox(lane_key(seed, gid), 0x5EED0000ull, c + (uint64_t)k);
+    if (k == 0) s.x = r.x;
+    s.d[k] = (uint16_t)dice_pack(die_from(r.x), die_from(r.y));
+}
+// the consumer (the interface lane_advance needs): draws 0 and 1 past the
+// slot's counter come from the slot, later ones (new_game's starter and
+// first-roll loops, the roll after a max_steps truncation) are evaluated at
+// their counter as LaneRng::next does, the key computed on that path only
+struct SlotRng {
+    uint64_t seed, ctr, base;   // base: the counter the slot was drawn at
+    uint32_t gid, x, dd;        // the global lane; the slot's words (dd = d[0] | d[1] << 16)
     DiceTab dt;
     bool exhausted = false;
-    BGX_DEV void refill() {
-        base = ctr;
-        batch = philox(key, 0x5EED0000ull, base + (uint64_t)(lane_id() & 31));
+    BGX_DEV void load(const DrawSlot& s, uint64_t c) {
+        x = s.x;
+        dd = (uint32_t)s.d[0] | ((uint32_t)s.d[1] << 16);
+        ctr = base = c;
     }
-    BGX_DEV u32x4 at(int k) const {   // counter base + k, k < 32 (uniform within the half)
-        const int src = (lane_id() & 32) + k;
-        return {(uint32_t)__shfl((int)batch.x, src, 64), (uint32_t)__shfl((int)batch.y, src, 64),
-                (uint32_t)__shfl((int)batch.z, src, 64), (uint32_t)__shfl((int)batch.w, src, 64)};
-    }
-    BGX_DEV u32x4 next() {
-        if (ctr - base >= 32u) refill();
-        const u32x4 r = at((int)(ctr - base));
-        ++ctr;
-        return r;
-    }
+    BGX_DEV float uniform01() const { return unit_from(x); }   // lane_uniform at the slot's counter
     BGX_DEV void roll(int& a, int& b) {
         if (dt.tab) { exhausted |= !dt.roll(ctr, a, b); return; }
-        u32x4 r = next();
-        a = die_from(r.x);
-        b = die_from(r.y);
+        const uint64_t k = ctr - base;
+        if (k < 2u) {
+            dice_unpack(dd >> (16 * (int)k), a, b);
+        } else {
+            const u32x4 r = philox(lane_key(seed, gid), 0x5EED0000ull, ctr);
+            a = die_from(r.x);
+            b = die_from(r.y);
+        }
+        ++ctr;
     }
     BGX_DEV void skip_uniform() { if (!dt.tab) ++ctr; }
 };

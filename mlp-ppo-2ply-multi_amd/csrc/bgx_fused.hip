@@ -15,10 +15,18 @@
 //      record, reset -- on the LDS-resident lane state), then step s + 1's
 //      tier-1 movegen jobs (one lane each, or two rule-mode non-doubles lanes
 //      in one wave, job_records_pair; in the wave's own LDS slice,
-//      bgx_movegen.h, afterstates into the lanes' candidate slots). A choice
-//      waits for the tiles holding its lanes' rows, a job for its lane's
-//      choice (LDS flags); the MFMA-bound tiles, the latency-bound choices and
-//      the issue-bound movegen jobs share the SIMDs.
+//      bgx_movegen.h, afterstates into the lanes' candidate slots), then one
+//      draw item: one wave evaluates Philox4x32-10 once for the whole
+//      workgroup, two counters per lane, the two draws a lane's next step can
+//      consume (its sampling uniform or the roll of a pass, and the roll
+//      after a move), into a slot per lane in LDS (DrawSlot, bgx_engine.h).
+//      The choice items read their lanes' slots and evaluate Philox
+//      themselves only past them (new_game, the roll after a truncation). A
+//      choice waits for the tiles holding its lanes' rows, a job for its
+//      lane's choice, the draw item for every lane's choice (LDS flags); the
+//      MFMA-bound tiles, the latency-bound choices and the issue-bound
+//      movegen jobs share the SIMDs, and the draws are made by a wave that
+//      would otherwise sit in the step's end barrier.
 // Replaces, per lane and step, Worker.play_episode's inner loop
 // (src/multi/worker.py:101-162) over BackgammonEnv.step / update_legal_moves
 // (src/environments/backgammon_env.py:130-308) and the policy forward
@@ -60,6 +68,7 @@ template <int FL> struct FusedTail {
     unsigned claim[FL];             // lane v's next tier-1 job is taken iff claim[v] == the step's tag
     int pre[FL + 1];                // MLP row prefix over the lanes
     uint32_t job[FL][8];            // the lanes' jobs: packed board words 0..6, player | d0 << 8 | d1 << 16
+    DrawSlot draw[FL];              // the lanes' Philox draws for their next step (the draw item, bgx_engine.h)
     LaneState st[FL];               // the lanes' state for the whole launch (written back at the end)
 };
 template <int FL> struct FCfg {
@@ -160,7 +169,8 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
     // development timers (f.prof): phase sums on thread 0, per-wave sums on lane 0
     unsigned long long ph[6] = {0, 0, 0, 0, 0, 0}, tc = 0, tw[4] = {0, 0, 0, 0}, t2c = 0, t3n = 0;
     unsigned long long tjd[4] = {0, 0, 0, 0};   // tier-1 job clocks / counts: doubles, non-doubles
-    unsigned long long tcs[3] = {0, 0, 0};      // choice: state + Philox refill, pick, env step (lane_advance)
+    unsigned long long tcs[3] = {0, 0, 0};      // choice: state + draw slot, pick, env step (lane_advance)
+    unsigned long long tdr[3] = {0, 0, 0};      // draw item: clocks, of them waiting for the choices, count
     unsigned long long tms[3] = {0, 0, 0};      // MLP tile: rows, MFMA chain issue, drain + epilogue
     // pairing: clocks / count of the non-doubles rule-mode two-move jobs run
     // alone; pipelined claims, those of a rule-mode non-doubles lane, and those
@@ -188,6 +198,15 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
     // is handed out before any job item, and a job item either claims a lane,
     // or sees all of the step's lanes claimed and ends as a no-op, or reaches
     // the poll bound (BGX_ERRF_WAIT_BOUND).
+    // The queue's last item, the draw item, draws the next step's Philox
+    // numbers of every lane (T.draw) and first waits, in the pipelined queue,
+    // until every lane of the step is stepped (T.chosen): a lane's counter is
+    // final only behind its own choice. It is handed out after every choice
+    // and every job item, the choices wait for tiles only and tiles for
+    // nothing, so its wait ends as theirs do (same bound, same flag); no item
+    // waits for it: the step's end barrier publishes the slots. Step -1's
+    // queue has one too (the launch's first step), with nothing to wait for,
+    // as in the three-pass form, whose choices are behind a barrier.
     // The MFMA-bound tiles, the latency-bound choice chains and the issue-bound
     // tier-1 jobs then share the SIMDs instead of running in barrier-separated
     // phases; the barriers left per step are the ones around the workgroup
@@ -360,8 +379,9 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                 const int qj = one || pass == 2 ? nj : 0;
                 const bool pipelined = one && np > 0;   // waits between items of the same queue
                 int* qc = &T.qn[pass & 1];
+                const int qd = pass == npass - 1 ? 1 : 0;   // the draw item, the queue's last
                 int it = w;
-                while (it < qt + qp + qj) {
+                while (it < qt + qp + qj + qd) {
                     if (it < qt) {
                         // ---- 3. one MLP tile: its 32 rows from the lanes' obs rows /
                         // candidate slots (L2), all four m-tiles in the wave (mlp_tile4)
@@ -430,11 +450,11 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                             LaneState sr = T.st[v];
                             const int n_full = T.cnt[v];
                             const int n = n_full < e.max_legal ? n_full : e.max_legal;
-                            HalfRng rng;
-                            rng.key = lane_key(e.seed, (uint32_t)(e.lane_base + i));
-                            rng.ctr = sr.ctr;
+                            SlotRng rng;   // this step's draws: made by the last step's draw item
+                            rng.seed = e.seed;
+                            rng.gid = (uint32_t)(e.lane_base + i);
                             rng.dt = lane_dice(e, i);
-                            rng.refill();
+                            rng.load(T.draw[v], sr.ctr);
                             unsigned long long c0 = 0;
                             if (prof) {
                                 __builtin_amdgcn_s_waitcnt(0);
@@ -447,7 +467,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                                 const float* xv = xs + v * XS;   // V(s), then V(candidate k) at 1 + k
                                 const float* vv = f.vbuf + (size_t)i * (f.cap + 1);
                                 const float Tm = e.temperature;
-                                const float u = unit_from(rng.at(0).x);   // lane_uniform: Philox at the lane's counter
+                                const float u = rng.uniform01();   // lane_uniform: Philox at the lane's counter
                                 const int pick =
                                     n + 1 <= XS
                                         ? pick_action_half([&](int kk) { return xv[1 + kk] / Tm; }, n, e.greedy != 0, u)
@@ -476,7 +496,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                         if (lead && v < hi)
                             __hip_atomic_store(&T.chosen[v], qtag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    } else {
+                    } else if (it < qt + qp + qj) {
                         // ---- 1. a tier-1 job of the next step in this wave's slice:
                         // lane order behind the choices (a lane's job waits for its
                         // choice), doubles first when the queue holds jobs only
@@ -612,6 +632,40 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                                     tpr[1] += 1;
                                 }
                             }
+                        }
+                    } else {
+                        // ---- 5. the draw item: the next step's Philox draws of every lane,
+                        // by one wave. Thread l draws for lane l % FL at the lane's counter
+                        // + (l / FL) (threads past 2 FL idle), once every lane's counter is
+                        // final: behind its choice in the pipelined queue, at once otherwise
+                        // (the choices are behind a barrier, or the step has none)
+                        const unsigned long long d0 = prof ? wall_clock64() : 0ull;
+                        const FusedArgs& f = launch_args();
+                        const int ld = lane_id();   // at use: nothing of the item is hoisted out of the loops
+                        const int v = ld & (FL - 1), k = ld / FL;
+                        const bool mine = k < 2 && act(v);
+                        if (pipelined) {
+                            for (unsigned spin = 0;; ++spin) {
+                                const bool pend =
+                                    mine &&
+                                    __hip_atomic_load(&T.chosen[v], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != qtag;
+                                if (!ballot(pend)) break;
+                                if (spin >= (1u << 24)) {   // bounded
+                                    if (l == 0) atomicOr(f.e.err_flags, BGX_ERRF_WAIT_BOUND);
+                                    break;
+                                }
+                                __builtin_amdgcn_s_sleep(1);
+                            }
+                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                        }
+                        const unsigned long long d1 = prof ? wall_clock64() : 0ull;
+                        if (mine)
+                            draw_fill(T.draw[v], f.e.seed, (uint32_t)(f.e.lane_base + g * FL + v), T.st[v].ctr, k);
+                        if (prof) {
+                            __builtin_amdgcn_s_waitcnt(0);
+                            tdr[0] += wall_clock64() - d0;
+                            tdr[1] += d1 - d0;
+                            tdr[2] += 1;
                         }
                     }
                     int kn = 0;
@@ -770,6 +824,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
             atomicAdd(P + 22, tms[1]);
             atomicAdd(P + 23, tms[2]);
             for (int k = 0; k < 7; ++k) atomicAdd(P + 88 + k, tpr[k]);
+            for (int k = 0; k < 3; ++k) atomicAdd(P + 95 + k, tdr[k]);
         }
     }
     if (t == 0) {

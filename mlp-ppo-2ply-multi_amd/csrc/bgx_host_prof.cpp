@@ -21,6 +21,12 @@ void fused_prof_report(const unsigned long long* p, int n_slots, FILE* out, cons
             (s[14] + s[16]) / n / 100, (s[8] + s[10] + s[14] + s[16]) / nws / 100, (int)(nws / n + 0.5));
     fprintf(out, "[bgx fused prof] choice per wave-step: state + Philox refill %.2f, pick %.2f, "
             "env step %.2f us\n", s[29] / nws / 100, s[30] / nws / 100, s[31] / nws / 100);
+    // the draw item (one per step queue, step -1's included; words 95..97:
+    // clocks, of them waiting for the step's choices, count); the first
+    // figure of the line above is the state load plus the slot read
+    fprintf(out, "[bgx fused prof] draw item: %.2f us each, %.2f of it waiting for the choices (%.0f items, "
+            "%.2f per workgroup step)\n", s[95] / (s[97] > 0 ? s[97] : 1) / 100,
+            s[96] / (s[97] > 0 ? s[97] : 1) / 100, s[97], s[97] / n);
     fprintf(out, "[bgx fused prof] MLP tiles per workgroup step: rows + k mask %.2f, MFMA chain issue %.2f, "
             "drain + epilogue %.2f wave-us\n", s[6] / n / 100, s[22] / n / 100, s[23] / n / 100);
     // step durations by index within a launch (every launch, every workgroup):
