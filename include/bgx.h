@@ -499,6 +499,48 @@ int bgx_td_update_batched(const uint32_t* d_records, const int32_t* d_offs, int 
                           float* d_target_out /* NULL, or [n_records]: G of every record */,
                           void* d_work, uint64_t work_bytes, void* stream);
 
+/* bgx_td_update_batched on afterstates, the positions the engine rates: 1-ply
+ * play picks a move by V of the board after it under the mover's indicator, and
+ * 2-ply scores the opponent's reply afterstates, while every other trainer here
+ * fits V on the board before the move. For record s of episode [a, b) the input
+ * row A_s (7 packed words) is
+ *   src    = words 0..6 of record s + 1             if s < b - 1
+ *            words 6..12 of header e (final board)  if s = b - 1
+ *   A_s[k] = src[k], k = 0..5
+ *   A_s[6] = (src[6] & 0xFFFF) | m_s << 16,  m_s = (record s word 11 >> 9) & 1
+ * (passes write no record, so record s + 1's before-board is the board after
+ * record s's move; whatever indicator src carries is ignored). Y_s = V(A_s) is
+ * the value to m_s of the position they leave, and the target recurrence is
+ * bgx_td_update_batched's on those Y, rewards and movers (record words 9 and 11)
+ * as they are; flags is 0 or BGX_TDF_ZERO_SUM. The index launch also writes one
+ * int32 per record, where its row comes from, and the forward and backward
+ * launches' afterstate instances load the rows through it (csrc/bgx_train_tile.h;
+ * no afterstate row is stored); everything downstream of the loader is
+ * bgx_td_update_batched's code, so the call leaves the bits that
+ * bgx_td_update_batched leaves on records whose words 0..6 were replaced by A_s
+ * (at lambda = 0 without the flag, too, the backward launch reads the target
+ * stage's G). Only header words 6..12 are read; d_offs stays the authority on
+ * episode bounds; a record in no episode takes no part. Nothing is read at or
+ * past d_records + 12 n_records or d_headers + 16 n_eps.
+ * d_work: 16-byte aligned, at least bgx_td_afterstate_batch_workspace(n_records)
+ * bytes (bgx_tdlambda_batch_workspace's layout, V of every record first, with
+ * the source index behind it). d_target_out, the metrics, determinism and
+ * asynchrony (no host synchronisation, no allocation, capturable) as
+ * bgx_td_update_batched.
+ * BGX_E_ARG: what bgx_td_update_batched rejects, a null d_headers, work_bytes
+ * below bgx_td_afterstate_batch_workspace; all before the device is touched. */
+int bgx_td_afterstate_update_batched(const uint32_t* d_records, const uint32_t* d_headers /* [n_eps][16] */,
+                                     const int32_t* d_offs, int n_eps, int n_records, float* d_params,
+                                     float* d_adam_m, float* d_adam_v, int* d_step, float lr, float gamma,
+                                     float lambda, uint32_t flags /* 0 or BGX_TDF_ZERO_SUM */, float grad_clip,
+                                     double* d_metrics,
+                                     float* d_grad_out   /* NULL, or [25601]: the pre-clip gradient, state_dict order */,
+                                     float* d_target_out /* NULL, or [n_records]: G of every record */,
+                                     void* d_work, uint64_t work_bytes, void* stream);
+/* bytes of device workspace bgx_td_afterstate_update_batched needs for n_records
+ * records (bgx_tdlambda_batch_workspace plus one int32 per record); pure host arithmetic */
+int bgx_td_afterstate_batch_workspace(int n_records, uint64_t* bytes);
+
 /* Copy-engine transfer helpers (bgx/hostgather.py: the episode gather of
  * the ranks of one node through host shared memory, replacing the pickled
  * queue of src/main.py:115-133 / multi/experience_queue.py:5-13 without

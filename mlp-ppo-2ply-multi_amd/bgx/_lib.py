@@ -98,6 +98,10 @@ SIGNATURES = {
     "bgx_td_update_batched": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_float, c_float, c_float, ctypes.c_uint32, c_float, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_u64, c_void_p]),
+    "bgx_td_afterstate_update_batched": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                                 c_void_p, c_void_p, c_float, c_float, c_float, ctypes.c_uint32,
+                                                 c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_void_p]),
+    "bgx_td_afterstate_batch_workspace": (c_int, [c_int, ctypes.POINTER(c_u64)]),
     "bgx_host_register": (c_int, [c_void_p, c_u64]),
     "bgx_host_unregister": (c_int, [c_void_p]),
     "bgx_copy_async": (c_int, [c_void_p, c_void_p, c_u64, c_int, c_void_p]),

@@ -67,6 +67,19 @@ def packed_before_after(headers: np.ndarray, rec: np.ndarray):
     return before, after
 
 
+def packed_afterstates(headers: np.ndarray, rec: np.ndarray) -> np.ndarray:
+    """Packed afterstate rows uint32 [m, 8] (host numpy): the board after every
+    record's move under the indicator of the record's own mover (word 11 bit 9),
+    the position the engine rates when it picks that move. The board is
+    packed_before_after's `after`; whatever indicator its source carries (the next
+    mover's in a record, the next_observation rule in a header) is ignored."""
+    r = np.ascontiguousarray(rec).view(np.uint32).reshape(-1, REC_WORDS)
+    after = packed_before_after(headers, r)[1]
+    mover = ((r[:, 11] >> 9) & 1).astype(np.uint32)
+    after[:, 6] = (after[:, 6] & 0xFFFF) | (mover << 16)
+    return after
+
+
 def pack_record(before_w, mover, v_s, v_a, reward, action, n_moves, step, dice, done, close_out, prime,
                 win_type):
     """One record (uint32 [12]) from its fields (tests, synthetic inputs)."""

@@ -8,7 +8,9 @@ use. No torch, no GPU, no libbgx.so.
 and of its TD(lambda) form (bgx_tdlambda_update_batched), whose target is the
 lambda-return of lambda_returns, with the zero-sum targets of
 bgx_td_update_batched (BGX_TDF_ZERO_SUM) as lambda_returns(movers=) /
-batched_td0_reference(zero_sum=True). batched_td0_reference states the forward pass and the gradient in float64;
+batched_td0_reference(zero_sum=True), and of bgx_td_afterstate_update_batched
+(the same update on afterstate rows) as batched_td0_reference(afterstates=True,
+headers=). batched_td0_reference states the forward pass and the gradient in float64;
 adam_reference states clip_grad_norm_ and the Adam step in float32, in the
 kernel's operation order, which is torch's (sqrt(v) / sqrt(bc2) + eps, then
 p + (-step_size m) / den, every operation correctly rounded).
@@ -43,6 +45,16 @@ def encode_records(records) -> np.ndarray:
     f[:, 196] = ind == 0
     f[:, 197] = ind == 1
     return f
+
+
+def encode_afterstates(headers, records) -> np.ndarray:
+    """The same encoding (float32 [m, 198]) of each record's afterstate row: the
+    board after its move under its own mover's indicator
+    (bgx.records.packed_afterstates; bgx_td_afterstate_update_batched)."""
+    from .records import packed_afterstates
+    r = np.ascontiguousarray(records).view(np.uint32).reshape(-1, 12).copy()
+    r[:, :7] = packed_afterstates(headers, r)[:, :7]
+    return encode_records(r)
 
 
 def split_params(params):
@@ -94,12 +106,14 @@ def lambda_returns(Y, rewards, offs, gamma, lam, movers=None):
     return G
 
 
-def batched_td0_reference(params, records, offs, gamma, lam=0.0, zero_sum=False):
+def batched_td0_reference(params, records, offs, gamma, lam=0.0, zero_sum=False, afterstates=False, headers=None):
     """float64 forward and gradient of the batched loss. params: 25,601 values in
     state_dict order; records [m, 12]; offs [E + 1] (episode e = records
     [offs[e], offs[e + 1]), each at least 1 long). lam != 0: the target is the
     lambda-return (lambda_returns on the detached Y). zero_sum: the zero-sum
-    target at every lam (lambda_returns with the movers of word 11). Returns dict(grad float64
+    target at every lam (lambda_returns with the movers of word 11). afterstates:
+    V is taken on each record's afterstate row (encode_afterstates; headers
+    [E, 16] is then required), the targets' recurrence is unchanged. Returns dict(grad float64
     [25601], loss, Y float64 [m], target, td_error, predicted_value, reward: the
     last three summed over episodes as the kernel's metrics are)."""
     W1, b1, w2, b2 = (np.asarray(x, np.float64) for x in split_params(params))
@@ -109,7 +123,9 @@ def batched_td0_reference(params, records, offs, gamma, lam=0.0, zero_sum=False)
     lens = np.diff(offs)
     if E < 1 or offs[0] != 0 or offs[-1] != r.shape[0] or (lens < 1).any():
         raise ValueError("offs: episodes must tile the records, each at least 1 long")
-    X = encode_records(r).astype(np.float64)
+    if afterstates and headers is None:
+        raise ValueError("afterstates=True needs the episode headers (the final boards)")
+    X = (encode_afterstates(headers, r) if afterstates else encode_records(r)).astype(np.float64)
     rew = r[:, 9].copy().view(np.float32).astype(np.float64)
     S = 1.0 / (1.0 + np.exp(-(X @ W1.T + b1)))
     Y = S @ w2 + b2

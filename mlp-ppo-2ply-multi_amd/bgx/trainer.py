@@ -44,6 +44,19 @@ backend honours it, sequential and batched; batched=True with backend="hip"
 runs bgx_td_update_batched with BGX_TDF_ZERO_SUM (the zero-sum instance of the
 target stage, at every lam). The sequential HIP kernel stays the reference's
 TD(0).
+
+afterstates (default False: V is fitted on the board before each move, as the
+reference's trainer does) fits V on the positions the engine rates instead:
+record s contributes V(A_s), A_s the board after its move under the indicator
+of its own mover (the next record's before-board, or the header's final board
+on an episode's last record; bgx.records.packed_afterstates). The targets'
+recurrence is unchanged, with Y_s = V(A_s): rewards, lam and zero_sum mean what
+they mean above. The torch backend honours it, sequential and batched (on the
+Episode path the row is next_observation with features 196 / 197 rewritten to
+the mover's, the mover taken from the observation's feature 197);
+batched=True with backend="hip" runs bgx_td_afterstate_update_batched at every
+lam / zero_sum. The sequential HIP kernel stays the reference's TD(0) on
+before-move positions.
 """
 from __future__ import annotations
 
@@ -52,7 +65,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .records import WIN_TYPES
+from .records import WIN_TYPES, packed_afterstates
 
 TDF_ZERO_SUM = 1   # BGX_TDF_ZERO_SUM (include/bgx.h)
 from .net import BackgammonPolicyNetwork
@@ -66,7 +79,7 @@ MIN_EPISODES_TO_TRAIN = 200   # configuration.py:7
 class DeviceTrainer:
     def __init__(self, parameter_manager, device=None, lr=LEARNING_RATE, gamma=GAMMA,
                  grad_clip=GRAD_CLIP_THRESHOLD, batch_episode_size=MIN_EPISODES_TO_TRAIN, batched=False,
-                 backend=None, lam=0.0, zero_sum=False):
+                 backend=None, lam=0.0, zero_sum=False, afterstates=False):
         self.parameter_manager = parameter_manager
         self.device = torch.device(device) if device is not None else torch.device("cuda")
         self.policy_network = BackgammonPolicyNetwork().to(self.device)
@@ -89,6 +102,9 @@ class DeviceTrainer:
         if not isinstance(zero_sum, (bool, np.bool_)):
             raise ValueError(f"zero_sum must be a bool, not {zero_sum!r}")
         self.zero_sum = bool(zero_sum)
+        if not isinstance(afterstates, (bool, np.bool_)):
+            raise ValueError(f"afterstates must be a bool, not {afterstates!r}")
+        self.afterstates = bool(afterstates)
         self.total_episodes = 0
         self._flat = None   # HIP backend state: params / Adam m / v (flat, state_dict order), step
         self._work = None   # batched HIP backend: the workspace tensor, regrown on demand
@@ -109,7 +125,11 @@ class DeviceTrainer:
         if rec.dtype != torch.int32:
             rec = rec.view(torch.int32) if rec.dtype == torch.uint32 else rec.to(torch.int32)
         before = torch.zeros((rec.shape[0], 8), dtype=torch.int32, device=self.device)
-        before[:, :7] = rec[:, :7]   # the board before the move, the mover's indicator (bgx/records.py)
+        if self.afterstates:   # the board after the move, the mover's indicator (records.packed_afterstates)
+            rows = packed_afterstates(np.asarray(torch.as_tensor(headers).cpu().numpy()), rec.cpu().numpy())
+            before[:, :7] = torch.from_numpy(rows[:, :7].view(np.int32)).to(self.device)
+        else:
+            before[:, :7] = rec[:, :7]   # the board before the move, the mover's indicator (bgx/records.py)
         obs = ops.encode_packed(before)
         rewards = rec[:, 9].contiguous().view(torch.float32)
         hdr = np.asarray(torch.as_tensor(headers).cpu().numpy()).astype(np.uint32)
@@ -135,8 +155,13 @@ class DeviceTrainer:
             lens.append(len(ep.experiences))
             wins.append(ep.win_type)
         obs_t = torch.stack(obs).to(self.device) if obs else torch.zeros((0, 198), device=self.device)
-        return (obs_t, torch.tensor(rew, dtype=torch.float32, device=self.device), lens, wins,
-                self._observation_movers(obs_t))
+        movers = self._observation_movers(obs_t)
+        if self.afterstates and obs:   # next_observation under the mover's indicator, not the next player's
+            nxt = [torch.as_tensor(np.asarray(x.next_observation, np.float32)) for ep in episodes for x in ep.experiences]
+            obs_t = torch.stack(nxt).to(self.device)
+            obs_t[:, 196] = (movers == 0).to(obs_t.dtype)
+            obs_t[:, 197] = (movers == 1).to(obs_t.dtype)
+        return obs_t, torch.tensor(rew, dtype=torch.float32, device=self.device), lens, wins, movers
 
     # ------------------------------------------------------------ update
     def update(self, episodes):
@@ -155,6 +180,10 @@ class DeviceTrainer:
             if self.zero_sum and not self.batched:
                 raise ValueError("the sequential HIP update (bgx_td0_update) keeps the reference's TD(0) target: for "
                                  "zero_sum=True use batched=True with backend='hip', or backend='torch'")
+            if self.afterstates and not self.batched:
+                raise ValueError("the sequential HIP update (bgx_td0_update) keeps the reference's before-move "
+                                 "positions: for afterstates=True use batched=True with backend='hip', or "
+                                 "backend='torch'")
             return self._update_hip_batched(headers, records) if self.batched else self._update_hip(headers, records)
         return self._update(*self._from_records(headers, records))
 
@@ -243,7 +272,8 @@ class DeviceTrainer:
 
     def _update_hip_batched(self, headers, records):
         """One bgx_td0_update_batched call (bgx_tdlambda_update_batched when
-        lam != 0, bgx_td_update_batched with BGX_TDF_ZERO_SUM when zero_sum):
+        lam != 0, bgx_td_update_batched with BGX_TDF_ZERO_SUM when zero_sum,
+        bgx_td_afterstate_update_batched at every lam / zero_sum when afterstates):
         one Adam step on the mean of the per-episode losses (the torch batched
         path's semantics)."""
         import ctypes
@@ -265,7 +295,10 @@ class DeviceTrainer:
         offs = torch.as_tensor(offs_h.astype(np.int32), device=self.device)
         f = self._hip_state()
         need = ctypes.c_uint64(0)
-        if self.lam != 0.0 or self.zero_sum:
+        if self.afterstates:
+            check(lib().bgx_td_afterstate_batch_workspace(n_rec, ctypes.byref(need)),
+                  "bgx_td_afterstate_batch_workspace")
+        elif self.lam != 0.0 or self.zero_sum:
             check(lib().bgx_tdlambda_batch_workspace(n_rec, ctypes.byref(need)), "bgx_tdlambda_batch_workspace")
         else:
             check(lib().bgx_td0_batch_workspace(n_rec, ctypes.byref(need)), "bgx_td0_batch_workspace")
@@ -276,7 +309,15 @@ class DeviceTrainer:
         lr = float(self.optimizer.param_groups[0]["lr"])
         with torch.cuda.device(self.device):   # the trainer's device and its current stream
             stream = stream_handle(torch.cuda.current_stream(self.device))
-            if self.zero_sum:
+            if self.afterstates:
+                d_hdr = torch.from_numpy(np.ascontiguousarray(hdr).view(np.int32)).to(self.device)
+                check(lib().bgx_td_afterstate_update_batched(ptr(rec), ptr(d_hdr), ptr(offs), n_eps, n_rec, ptr(f["p"]),
+                                                             ptr(f["m"]), ptr(f["v"]), ptr(f["step"]), lr,
+                                                             float(self.gamma), self.lam,
+                                                             TDF_ZERO_SUM if self.zero_sum else 0, clip, ptr(metrics),
+                                                             None, None, ptr(self._work), self._work.numel(), stream),
+                      "bgx_td_afterstate_update_batched")
+            elif self.zero_sum:
                 check(lib().bgx_td_update_batched(ptr(rec), ptr(offs), n_eps, n_rec, ptr(f["p"]), ptr(f["m"]),
                                                   ptr(f["v"]), ptr(f["step"]), lr, float(self.gamma), self.lam,
                                                   TDF_ZERO_SUM, clip, ptr(metrics), None, None, ptr(self._work),

@@ -345,25 +345,30 @@ int bgx_td0_batch_shape(int* tile, int* grid) {
     });
 }
 
-// the batched update behind both entry points; lam: the TD(lambda) one (its
+// the batched update behind all its entry points; lam: the TD(lambda) ones (their
 // workspace carries the targets after the TD(0) layout); flags: BGX_TDF_* (the
-// lambda one only)
-static int update_batched(const char* name, bool lam, const uint32_t* d_records, const int32_t* d_offs, int n_eps,
+// lambda ones only); after: the afterstate one (d_headers required, the source
+// index behind the targets)
+static int update_batched(const char* name, bool lam, bool after, const uint32_t* d_records,
+                          const uint32_t* d_headers, const int32_t* d_offs, int n_eps,
                           int n_records, float* d_params, float* d_adam_m, float* d_adam_v, int* d_step, float lr,
                           float gamma, float lambda, uint32_t flags, float grad_clip, double* d_metrics,
                           float* d_grad_out, float* d_target_out, void* d_work, uint64_t work_bytes, void* stream) {
     return guarded(name, [&]() -> int {
         if (n_eps <= 0 || n_records < n_eps) return fail(BGX_E_ARG, "%s: n_eps=%d n_records=%d", name, n_eps, n_records);
-        if (!d_records || !d_offs || !d_params || !d_adam_m || !d_adam_v || !d_step || !d_metrics || !d_work)
+        if (!d_records || !d_offs || !d_params || !d_adam_m || !d_adam_v || !d_step || !d_metrics || !d_work ||
+            (after && !d_headers))
             return fail(BGX_E_ARG, "%s: null pointer", name);
         if (lam && !(lambda >= 0.0f && lambda <= 1.0f))   // a NaN fails both comparisons
             return fail(BGX_E_ARG, "%s: lambda=%g is not in [0, 1]", name, (double)lambda);
         if (flags & ~(uint32_t)BGX_TDF_ZERO_SUM) return fail(BGX_E_ARG, "%s: unknown flags=0x%x", name, (unsigned)flags);
         const bgx::TrainBatchLayout l = bgx::train_batch_layout(n_records);
-        const uint64_t need = lam ? l.bytes_lambda : l.bytes;
+        const uint64_t need = after ? l.bytes_after : lam ? l.bytes_lambda : l.bytes;
         if (work_bytes < need)
             return fail(BGX_E_ARG, "%s: work_bytes=%llu < %llu (%s)", name, (unsigned long long)work_bytes,
-                        (unsigned long long)need, lam ? "bgx_tdlambda_batch_workspace" : "bgx_td0_batch_workspace");
+                        (unsigned long long)need,
+                        after ? "bgx_td_afterstate_batch_workspace"
+                              : lam ? "bgx_tdlambda_batch_workspace" : "bgx_td0_batch_workspace");
         if ((uintptr_t)d_work % 16 != 0) return fail(BGX_E_ARG, "%s: d_work is not 16-byte aligned", name);
         DeviceScope ds(d_params);   // the kernels run on the device holding the parameters
         HIP_TRY(ds.err);
@@ -394,6 +399,14 @@ static int update_batched(const char* name, bool lam, const uint32_t* d_records,
             a.target_out = d_target_out;
             a.zero_sum = (flags & BGX_TDF_ZERO_SUM) ? 1 : 0;
         }
+        if (after) {
+            bgx::TrainAfterBatchArgs x{};
+            static_cast<bgx::TrainBatchArgs&>(x) = a;
+            x.hdr = d_headers;
+            x.srcidx = (int32_t*)(w + l.srcidx);
+            HIP_TRY(bgx_launch_td_after_batched(&x, (hipStream_t)stream));
+            return BGX_OK;
+        }
         HIP_TRY(bgx_launch_td0_batched(&a, (hipStream_t)stream));
         return BGX_OK;
     });
@@ -403,9 +416,9 @@ int bgx_td0_update_batched(const uint32_t* d_records, const int32_t* d_offs, int
                            float* d_params, float* d_adam_m, float* d_adam_v, int* d_step, float lr, float gamma,
                            float grad_clip, double* d_metrics, float* d_grad_out, void* d_work, uint64_t work_bytes,
                            void* stream) {
-    return update_batched("bgx_td0_update_batched", false, d_records, d_offs, n_eps, n_records, d_params, d_adam_m,
-                          d_adam_v, d_step, lr, gamma, 0.0f, 0u, grad_clip, d_metrics, d_grad_out, nullptr, d_work,
-                          work_bytes, stream);
+    return update_batched("bgx_td0_update_batched", false, false, d_records, nullptr, d_offs, n_eps, n_records,
+                          d_params, d_adam_m, d_adam_v, d_step, lr, gamma, 0.0f, 0u, grad_clip, d_metrics, d_grad_out,
+                          nullptr, d_work, work_bytes, stream);
 }
 
 int bgx_tdlambda_batch_workspace(int n_records, uint64_t* bytes) {
@@ -420,18 +433,37 @@ int bgx_tdlambda_update_batched(const uint32_t* d_records, const int32_t* d_offs
                                 float* d_params, float* d_adam_m, float* d_adam_v, int* d_step, float lr,
                                 float gamma, float lambda, float grad_clip, double* d_metrics, float* d_grad_out,
                                 float* d_target_out, void* d_work, uint64_t work_bytes, void* stream) {
-    return update_batched("bgx_tdlambda_update_batched", true, d_records, d_offs, n_eps, n_records, d_params,
-                          d_adam_m, d_adam_v, d_step, lr, gamma, lambda, 0u, grad_clip, d_metrics, d_grad_out,
-                          d_target_out, d_work, work_bytes, stream);
+    return update_batched("bgx_tdlambda_update_batched", true, false, d_records, nullptr, d_offs, n_eps, n_records,
+                          d_params, d_adam_m, d_adam_v, d_step, lr, gamma, lambda, 0u, grad_clip, d_metrics,
+                          d_grad_out, d_target_out, d_work, work_bytes, stream);
 }
 
 int bgx_td_update_batched(const uint32_t* d_records, const int32_t* d_offs, int n_eps, int n_records,
                           float* d_params, float* d_adam_m, float* d_adam_v, int* d_step, float lr, float gamma,
                           float lambda, uint32_t flags, float grad_clip, double* d_metrics, float* d_grad_out,
                           float* d_target_out, void* d_work, uint64_t work_bytes, void* stream) {
-    return update_batched("bgx_td_update_batched", true, d_records, d_offs, n_eps, n_records, d_params, d_adam_m,
-                          d_adam_v, d_step, lr, gamma, lambda, flags, grad_clip, d_metrics, d_grad_out, d_target_out,
-                          d_work, work_bytes, stream);
+    return update_batched("bgx_td_update_batched", true, false, d_records, nullptr, d_offs, n_eps, n_records,
+                          d_params, d_adam_m, d_adam_v, d_step, lr, gamma, lambda, flags, grad_clip, d_metrics,
+                          d_grad_out, d_target_out, d_work, work_bytes, stream);
+}
+
+int bgx_td_afterstate_batch_workspace(int n_records, uint64_t* bytes) {
+    return guarded("bgx_td_afterstate_batch_workspace", [&]() -> int {
+        if (n_records <= 0 || !bytes)
+            return fail(BGX_E_ARG, "bgx_td_afterstate_batch_workspace: n_records=%d", n_records);
+        *bytes = bgx::train_batch_layout(n_records).bytes_after;
+        return BGX_OK;
+    });
+}
+
+int bgx_td_afterstate_update_batched(const uint32_t* d_records, const uint32_t* d_headers, const int32_t* d_offs,
+                                     int n_eps, int n_records, float* d_params, float* d_adam_m, float* d_adam_v,
+                                     int* d_step, float lr, float gamma, float lambda, uint32_t flags,
+                                     float grad_clip, double* d_metrics, float* d_grad_out, float* d_target_out,
+                                     void* d_work, uint64_t work_bytes, void* stream) {
+    return update_batched("bgx_td_afterstate_update_batched", true, true, d_records, d_headers, d_offs, n_eps,
+                          n_records, d_params, d_adam_m, d_adam_v, d_step, lr, gamma, lambda, flags, grad_clip,
+                          d_metrics, d_grad_out, d_target_out, d_work, work_bytes, stream);
 }
 
 int bgx_reply_moves(const uint8_t* d_boards, const uint8_t* d_opponent, int n, uint32_t* d_out, int cap,

@@ -330,10 +330,17 @@ struct TrainBatchArgs {
     // enter as 1 - x where the mover (word 11 bit 9) changes; the target stage then runs at every lambda
     int zero_sum;
 };
+// TrainBatchArgs for afterstate rows (bgx_td_afterstate_update_batched; bgx_train_tile.h). The base keeps
+// its layout: the kernels that know no afterstates take it as it was
+struct TrainAfterBatchArgs : TrainBatchArgs {
+    const uint32_t* hdr;         // [n_eps][16] episode headers: words 6..12, the final board, are read
+    int32_t* srcidx;             // workspace [n_rec]: where a record's row comes from (tb_index<true>)
+};
 // byte offsets of the workspace's parts (each 16-byte aligned) and its size;
-// tgt follows the TD(0) call's workspace (bytes), bytes_lambda includes it
+// tgt follows the TD(0) call's workspace (bytes), bytes_lambda includes it;
+// srcidx follows that, bytes_after includes it
 struct TrainBatchLayout {
-    uint64_t Y, info, partial, grad, mpart, sqpart, bytes, tgt, bytes_lambda;
+    uint64_t Y, info, partial, grad, mpart, sqpart, bytes, tgt, bytes_lambda, srcidx, bytes_after;
 };
 inline TrainBatchLayout train_batch_layout(int n_rec) {
     const uint64_t n4 = ((uint64_t)n_rec + 3) / 4 * 4;
@@ -347,6 +354,8 @@ inline TrainBatchLayout train_batch_layout(int n_rec) {
     l.bytes = l.sqpart + (uint64_t)TRAIN_BATCH_SQ * 8;
     l.tgt = l.bytes;
     l.bytes_lambda = l.tgt + 4 * n4;
+    l.srcidx = l.bytes_lambda;
+    l.bytes_after = l.srcidx + 4 * n4;
     return l;
 }
 
@@ -391,6 +400,8 @@ hipError_t bgx_launch_top5(const float* V, const int32_t* job_off, const int32_t
 hipError_t bgx_launch_two_ply_reduce(const float* job_val, int n, double* out, hipStream_t stream);
 hipError_t bgx_launch_td0(const bgx::TrainArgs* args, hipStream_t stream);
 hipError_t bgx_launch_td0_batched(const bgx::TrainBatchArgs* args, hipStream_t stream);
+// the same on afterstate rows; args->tgt must be set (the backward launch reads the target stage's G)
+hipError_t bgx_launch_td_after_batched(const bgx::TrainAfterBatchArgs* args, hipStream_t stream);
 // tgt[s] (and target_out[s]) = the lambda-return of every record in an episode, 0 elsewhere;
 // reads Y, so it goes between the forward and the backward launch (bgx_train_lambda.hip)
 hipError_t bgx_launch_lambda_targets(const bgx::TrainBatchArgs* args, hipStream_t stream);

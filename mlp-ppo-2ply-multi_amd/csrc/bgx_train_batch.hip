@@ -42,15 +42,25 @@
 //             the tile's packed words and a [224][16] nibble -> value table in LDS (rows of 17 words).
 //             7 accumulator tiles (224 >= 198 features) per wave.
 // Nothing episode-sized lives in LDS: no episode-length limit.
+//
+// bgx_td_afterstate_update_batched is bgx_td_update_batched on afterstate rows: V
+// is fitted on the board each mover leaves, under the mover's indicator, the
+// positions the engine rates. The index, forward and backward kernels are
+// templates on their argument struct; with TrainAfterBatchArgs the index launch
+// also writes where each record's row comes from (the next record, or the episode
+// header's final board) and the forward and backward launches load those rows
+// (bgx_train_tile.h). Nothing else differs: everything downstream of the loader
+// is the same code, and the backward launch always reads the target stage's G.
+#include <type_traits>
+
 #include "bgx_device.h"
 #include "bgx_kernels.h"
+#include "bgx_train_tile.h"
 
 namespace bgx {
 
 namespace {
 
-constexpr int TB_T = 256;                          // threads of every launch here
-constexpr int TB_TILE = TRAIN_BATCH_TILE;          // records per tile
 constexpr int TB_C = TB_TILE / 32;                 // 32-record chunks per tile
 constexpr int TB_KS = 99;                          // forward k-steps (198 features, 2 per step)
 constexpr int TB_NT = 7;                           // backward feature tiles of 32
@@ -101,14 +111,15 @@ BGX_DEV float tb_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 // accumulator register t of lane half h holds row (record) ...
 BGX_DEV constexpr int tb_row(int t, int h) { return (t & 3) + 8 * (t >> 2) + 4 * h; }
 
-// the tile's records into LDS: words 0..6 (the board before the move, the
-// mover's flag) and the reward in slot 7; zeros past the last record
-BGX_DEV void tb_load_tile(const uint32_t* rec, int n_rec, long long base, uint32_t (*RW)[8]) {
-    for (int idx = (int)threadIdx.x; idx < TB_TILE * 8; idx += TB_T) {
-        const int r = idx >> 3, k = idx & 7;
-        const long long s = base + r;
-        RW[r][k] = s < n_rec ? rec[(size_t)s * 12 + (k < 7 ? k : 9)] : 0u;
-    }
+template <class Args>
+constexpr bool tb_after = std::is_same_v<Args, TrainAfterBatchArgs>;
+
+// the tile's rows into LDS: the records' own words, or their afterstate rows
+// (SRC: the tile's source indices, bgx_train_tile.h)
+template <class Args>
+BGX_DEV void tb_load_rows(const Args& a, const int32_t* SRC, long long base, uint32_t (*RW)[8]) {
+    if constexpr (tb_after<Args>) tb_load_tile_after(a.rec, a.hdr, SRC, a.n_rec, base, RW);
+    else tb_load_tile(a.rec, a.n_rec, base, RW);
 }
 
 // k-steps S .. TB_KS - 1 of the forward GEMM (a compile-time chain: W[S] and the
@@ -187,19 +198,15 @@ BGX_DEV double tb_block_sum(double v, double* red) {
 }  // namespace
 
 // ---------------------------------------------------------------- index
-__global__ __launch_bounds__(TB_T) void tb_index_kernel(TrainBatchArgs a) {
-    const int e = (int)(blockIdx.x * TB_T + threadIdx.x);
-    if (e == 0) *a.step += 1;
-    if (e >= a.n_eps) return;
-    int lo = a.offs[e], hi = a.offs[e + 1];
-    lo = lo < 0 ? 0 : (lo > a.n_rec ? a.n_rec : lo);
-    hi = hi < 0 ? 0 : (hi > a.n_rec ? a.n_rec : hi);
-    const int T = hi - lo;
-    for (int s = lo; s < hi; ++s) a.info[s] = T | (s == hi - 1 ? (int)0x80000000u : 0);
+template <class Args>
+__global__ __launch_bounds__(TB_T) void tb_index_kernel(Args a) {
+    if constexpr (tb_after<Args>) tb_index<true>(a, a.srcidx);
+    else tb_index<false>(a, nullptr);
 }
 
 // ---------------------------------------------------------------- forward
-__global__ __launch_bounds__(TB_T) void tb_forward_kernel(TrainBatchArgs a) {
+template <class Args>
+__global__ __launch_bounds__(TB_T) void tb_forward_kernel(Args a) {
     __shared__ __attribute__((aligned(16))) uint32_t RW[TB_TILE][8];
     __shared__ float P[TB_TILE][65];    // w2_j S[record][j], units j and j + 16 of a wave summed (65: conflict-free columns)
     __shared__ float off15[16];
@@ -210,11 +217,16 @@ __global__ __launch_bounds__(TB_T) void tb_forward_kernel(TrainBatchArgs a) {
     tb_load_w(a.params, wave, lane, W);
     const float b1v = a.params[TB_NW1 + unit], w2v = a.params[TB_NW1 + 128 + unit];
     const float b2 = a.params[TB_NW1 + 256];
+    __shared__ int32_t SRC[TB_TILE];   // afterstate rows only
+    if constexpr (tb_after<Args>) tb_stage_src(a.srcidx, a.n_rec, (long long)blockIdx.x * TB_TILE, SRC);
     for (int tile = (int)blockIdx.x; tile < a.n_tiles; tile += (int)gridDim.x) {
         const long long base = (long long)tile * TB_TILE;
+        if constexpr (tb_after<Args>) __builtin_amdgcn_s_waitcnt(0xF70);   // vmcnt(0): the requested SRC entries are in LDS
         __syncthreads();   // the previous tile's P / RW readers are done
-        tb_load_tile(a.rec, a.n_rec, base, RW);
+        tb_load_rows(a, SRC, base, RW);
         __syncthreads();
+        if constexpr (tb_after<Args>)   // the next tile's, under this tile's MFMA chains
+            tb_stage_src(a.srcidx, a.n_rec, base + (long long)gridDim.x * TB_TILE, SRC);
         f32x16 acc[TB_C];
         tb_forward(W, b1v, RW, off15, lane, acc);
 #pragma unroll
@@ -236,8 +248,8 @@ __global__ __launch_bounds__(TB_T) void tb_forward_kernel(TrainBatchArgs a) {
 
 // ---------------------------------------------------------------- backward
 // LAM: the target is the target stage's tgt[s] (TD(lambda)), not the inline TD(0) one
-template <bool LAM>
-__global__ __launch_bounds__(TB_T) void tb_backward_kernel(TrainBatchArgs a) {
+template <bool LAM, class Args>
+__global__ __launch_bounds__(TB_T) void tb_backward_kernel(Args a) {
     __shared__ __attribute__((aligned(16))) uint32_t RW[TB_TILE][8];
     __shared__ __attribute__((aligned(16))) float D[TB_TILE];   // dL/dY of the tile's records
     __shared__ float LUT[32 * TB_NT][TB_LUTW];   // rows padded to 17: a lane per row, conflict-free
@@ -278,11 +290,14 @@ __global__ __launch_bounds__(TB_T) void tb_backward_kernel(TrainBatchArgs a) {
     float gb1 = 0.0f, gw2 = 0.0f, gb2 = 0.0f;
     double m_loss = 0.0, m_td = 0.0, m_y = 0.0, m_rw = 0.0;   // threads < TB_TILE: their records' shares
     const float n_eps = (float)a.n_eps;
+    __shared__ int32_t SRC[TB_TILE];   // afterstate rows only
+    if constexpr (tb_after<Args>) tb_stage_src(a.srcidx, a.n_rec, (long long)blockIdx.x * TB_TILE, SRC);
 
     for (int tile = (int)blockIdx.x; tile < a.n_tiles; tile += (int)gridDim.x) {
         const long long base = (long long)tile * TB_TILE;
+        if constexpr (tb_after<Args>) __builtin_amdgcn_s_waitcnt(0xF70);   // vmcnt(0): the requested SRC entries are in LDS
         __syncthreads();   // the previous tile's readers are done
-        tb_load_tile(a.rec, a.n_rec, base, RW);
+        tb_load_rows(a, SRC, base, RW);
         if (t < TB_TILE) {
             const long long s = base + t;
             float d = 0.0f;
@@ -309,6 +324,8 @@ __global__ __launch_bounds__(TB_T) void tb_backward_kernel(TrainBatchArgs a) {
             D[t] = d;
         }
         __syncthreads();
+        if constexpr (tb_after<Args>)   // the next tile's, under this tile's MFMA chains
+            tb_stage_src(a.srcidx, a.n_rec, base + (long long)gridDim.x * TB_TILE, SRC);
         f32x16 acc[TB_C];
         tb_forward(W, b1v, RW, off15, lane, acc);
         // dL/dh in place (torch's sigmoid_backward order), and the small gradients
@@ -437,8 +454,8 @@ extern "C" hipError_t bgx_launch_td0_batched(const bgx::TrainBatchArgs* args, hi
     a.grid = a.n_tiles < TRAIN_BATCH_GRID ? a.n_tiles : TRAIN_BATCH_GRID;
     hipError_t e = hipMemsetAsync(a.info, 0, (size_t)a.n_rec * sizeof(int32_t), stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(tb_index_kernel, dim3((a.n_eps + TB_T - 1) / TB_T), dim3(TB_T), 0, stream, a);
-    hipLaunchKernelGGL(tb_forward_kernel, dim3(a.grid), dim3(TB_T), 0, stream, a);
+    hipLaunchKernelGGL(tb_index_kernel<TrainBatchArgs>, dim3((a.n_eps + TB_T - 1) / TB_T), dim3(TB_T), 0, stream, a);
+    hipLaunchKernelGGL(tb_forward_kernel<TrainBatchArgs>, dim3(a.grid), dim3(TB_T), 0, stream, a);
     // TD(lambda): the target stage, then the backward launch on its targets. lambda = 0
     // keeps the TD(0) backward launch (the same bits by construction); the stage then
     // runs only to fill target_out. Zero-sum targets: the inline TD(0) target knows no
@@ -449,9 +466,33 @@ extern "C" hipError_t bgx_launch_td0_batched(const bgx::TrainBatchArgs* args, hi
         e = bgx_launch_lambda_targets(&a, stream);
         if (e != hipSuccess) return e;
     }
-    if (lam) hipLaunchKernelGGL(tb_backward_kernel<true>, dim3(a.grid), dim3(TB_T), 0, stream, a);
-    else hipLaunchKernelGGL(tb_backward_kernel<false>, dim3(a.grid), dim3(TB_T), 0, stream, a);
+    if (lam) hipLaunchKernelGGL((tb_backward_kernel<true, TrainBatchArgs>), dim3(a.grid), dim3(TB_T), 0, stream, a);
+    else hipLaunchKernelGGL((tb_backward_kernel<false, TrainBatchArgs>), dim3(a.grid), dim3(TB_T), 0, stream, a);
     hipLaunchKernelGGL(tb_reduce_kernel, dim3(TB_NB), dim3(TB_T), 0, stream, a);
     hipLaunchKernelGGL(tb_adam_kernel, dim3(TB_NB), dim3(TB_T), 0, stream, a);
+    return hipGetLastError();
+}
+
+// the same launches on afterstate rows (bgx_train_tile.h): the index launch also
+// fills srcidx, the target stage runs at every lambda and flag, untouched (it
+// reads movers and rewards from record words 11 and 9, which afterstates do not
+// alter), and the backward launch reads its targets
+extern "C" hipError_t bgx_launch_td_after_batched(const bgx::TrainAfterBatchArgs* args, hipStream_t stream) {
+    using namespace bgx;
+    TrainAfterBatchArgs a = *args;
+    if (!a.tgt || !a.hdr || !a.srcidx) return hipErrorInvalidValue;
+    a.n_tiles = (int)(((long long)a.n_rec + TB_TILE - 1) / TB_TILE);
+    a.grid = a.n_tiles < TRAIN_BATCH_GRID ? a.n_tiles : TRAIN_BATCH_GRID;
+    hipError_t e = hipMemsetAsync(a.info, 0, (size_t)a.n_rec * sizeof(int32_t), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(a.srcidx, 0, (size_t)a.n_rec * sizeof(int32_t), stream);
+    if (e != hipSuccess) return e;
+    const TrainBatchArgs& b = a;   // the launches that know no afterstates
+    hipLaunchKernelGGL(tb_index_kernel<TrainAfterBatchArgs>, dim3((a.n_eps + TB_T - 1) / TB_T), dim3(TB_T), 0, stream, a);
+    hipLaunchKernelGGL(tb_forward_kernel<TrainAfterBatchArgs>, dim3(a.grid), dim3(TB_T), 0, stream, a);
+    e = bgx_launch_lambda_targets(&b, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((tb_backward_kernel<true, TrainAfterBatchArgs>), dim3(a.grid), dim3(TB_T), 0, stream, a);
+    hipLaunchKernelGGL(tb_reduce_kernel, dim3(TB_NB), dim3(TB_T), 0, stream, b);
+    hipLaunchKernelGGL(tb_adam_kernel, dim3(TB_NB), dim3(TB_T), 0, stream, b);
     return hipGetLastError();
 }

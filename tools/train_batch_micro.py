@@ -7,6 +7,9 @@ episodes (repeated to reach the larger sizes), then per size
                 records in the same process, event-timed the same way
   zero_sum_hip  (--lam L --zero-sum) one bgx_td_update_batched call with
                 BGX_TDF_ZERO_SUM, likewise
+  afterstate_hip (--lam L --zero-sum --afterstates) one
+                bgx_td_afterstate_update_batched call with BGX_TDF_ZERO_SUM on
+                the same records and their headers, likewise
   sequential    one bgx_td0_update call on the same records, event-timed
   batched_torch DeviceTrainer(batched=True, backend="torch").update_records,
                 wall clock around a synchronize (an eager path: its host work
@@ -89,9 +92,13 @@ def main():
                     help="also time bgx_tdlambda_update_batched with this lambda beside the TD(0) call")
     ap.add_argument("--zero-sum", action="store_true",
                     help="with --lam: also time bgx_td_update_batched with BGX_TDF_ZERO_SUM beside the lambda call")
+    ap.add_argument("--afterstates", action="store_true",
+                    help="with --lam --zero-sum: also time bgx_td_afterstate_update_batched beside the zero-sum call")
     args = ap.parse_args()
     if args.zero_sum and args.lam is None:
         ap.error("--zero-sum needs --lam")
+    if args.afterstates and not args.zero_sum:
+        ap.error("--afterstates needs --lam and --zero-sum")
     dev =torch.device("cuda")
     torch.manual_seed(0)
     pm, hdr_all, rec_all = harvest(max(args.sizes))
@@ -148,6 +155,23 @@ def main():
                 row["zero_sum_hip"] = {"lam": args.lam, "ms": ms_z, "episodes_per_s": n_eps / ms_z * 1e3,
                                        "records_per_s": n_rec / ms_z * 1e3, "over_lambda": ms_z / ms_l,
                                        "extra_us": (ms_z - ms_l) * 1e3}
+                if args.afterstates:
+                    # ---- the afterstate call: the zero-sum call's launches on afterstate rows
+                    p, m, v, step = flat_state(pm, dev)
+                    d_hdr = hdr.to(torch.int32).contiguous().to(dev)
+                    need_a = ctypes.c_uint64(0)
+                    check(L.bgx_td_afterstate_batch_workspace(n_rec, ctypes.byref(need_a)))
+                    work_a = torch.empty(need_a.value, dtype=torch.uint8, device=dev)
+
+                    def batched_afterstate():
+                        check(L.bgx_td_afterstate_update_batched(ptr(rec), ptr(d_hdr), ptr(offs), n_eps, n_rec, ptr(p),
+                                                                 ptr(m), ptr(v), ptr(step), 1e-3, 0.99, args.lam, 1, 1.0,
+                                                                 ptr(met), None, None, ptr(work_a), need_a.value, s))
+
+                    ms_a = event_ms(batched_afterstate, args.reps)
+                    row["afterstate_hip"] = {"lam": args.lam, "ms": ms_a, "episodes_per_s": n_eps / ms_a * 1e3,
+                                             "records_per_s": n_rec / ms_a * 1e3, "over_zero_sum": ms_a / ms_z,
+                                             "extra_us": (ms_a - ms_z) * 1e3}
         if args.only is None:
             # ---- the sequential kernel (one Adam step per episode)
             p, m, v, step = flat_state(pm, dev)

@@ -4,8 +4,9 @@ rows 1-3 together): the engine plays, every finished episode's compact
 records feed DeviceTrainer.update_records in the reference's batches of 200
 (--episodes-per-update N for others; --batched --backend hip for the multi-CU update;
 --lam L for TD(lambda) targets and --zero-sum for targets that take the next
-record from the opponent's side where the mover changes, both with --batched
---backend hip or --backend torch), and each update's weights go straight back
+record from the opponent's side where the mover changes, --afterstates to fit V
+on the board after each move under the mover's indicator, the positions the
+engine rates; all three with --batched --backend hip or --backend torch), and each update's weights go straight back
 into the engine with the reference temperature schedule
 (ParameterManager.get_temperature). --eval-games G then plays the final weights
 against the initial ones (bgx.match.play, 1-ply greedy) and adds games, ppg and
@@ -59,6 +60,8 @@ def main():
                     help="lambda of the lambda-return targets (0: TD(0), the reference's)")
     ap.add_argument("--zero-sum", action="store_true",
                     help="zero-sum targets (DeviceTrainer zero_sum=True): 1 - x of the next record where the mover changes")
+    ap.add_argument("--afterstates", action="store_true",
+                    help="fit V on afterstates (DeviceTrainer afterstates=True): the board after each move, the mover's indicator")
     ap.add_argument("--eval-games", type=int, default=0, metavar="G",
                     help="after the last update: G games of the final weights against the initial ones, 1-ply greedy")
     ap.add_argument("--save", default=None, metavar="PATH", help="write the final weights (W1 b1 w2 b2) to this .npz")
@@ -67,7 +70,7 @@ def main():
     torch.manual_seed(0)
     pm = LocalPM(BackgammonPolicyNetwork().state_dict())
     trainer = DeviceTrainer(pm, device="cuda", batch_episode_size=per, batched=args.batched, backend=args.backend,
-                            lam=args.lam, zero_sum=args.zero_sum)
+                            lam=args.lam, zero_sum=args.zero_sum, afterstates=args.afterstates)
     eng = Engine(lanes=args.lanes, seed=0)
     w = dict(zip(("W1", "b1", "w2", "b2"), weights_from(pm.get_parameters())))
     w_init = {k: np.array(v, copy=True) for k, v in w.items()}
@@ -108,6 +111,7 @@ def main():
                       "train_episodes_per_s": per * done / t_train, "train_share": t_train / el, "last_loss": m["loss"],
                       "version": pm.version, "temperature": pm.get_temperature(), "batched": args.batched,
                       "backend": trainer.backend, "episodes_per_update": per, "lam": trainer.lam, "zero_sum": trainer.zero_sum,
+                      "afterstates": trainer.afterstates,
                       **out}))
 
 
