@@ -244,7 +244,6 @@ class DeviceTrainer:
         f["token"] = self._module_token()
 
     def _update_hip(self, headers, records):
-        from ._lib import check, lib, ptr, stream_handle
         rec = torch.as_tensor(records).to(self.device)
         if rec.dtype != torch.int32:
             rec = rec.view(torch.int32) if rec.dtype == torch.uint32 else rec.to(torch.int32)
@@ -257,7 +256,13 @@ class DeviceTrainer:
             # the kernel skips an empty episode (no Adam step), while the metrics
             # below divide by every episode: reject it instead of skewing them
             raise ValueError("bgx_td0_update: an episode has no records")
-        offs = torch.as_tensor(np.concatenate([[0], np.cumsum(lens)]).astype(np.int32), device=self.device)
+        offs_h = np.concatenate([[0], np.cumsum(lens)])
+        n_rec = int(rec.shape[0])
+        if int(offs_h[-1]) != n_rec or n_rec >= 2 ** 31:
+            # the kernel reads records [0, offs[-1]): fewer than that would be read past the tensor's end
+            raise ValueError(f"bgx_td0_update: the headers count {int(offs_h[-1])} records, got {n_rec}")
+        from ._lib import check, lib, ptr, stream_handle
+        offs = torch.as_tensor(offs_h.astype(np.int32), device=self.device)
         f = self._hip_state()
         metrics = torch.zeros(5, dtype=torch.float64, device=self.device)
         n_eps = len(lens)

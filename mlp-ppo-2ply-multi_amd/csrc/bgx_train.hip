@@ -194,6 +194,12 @@ __global__ __launch_bounds__(TR_T) void td0_train_kernel(TrainArgs a) {
                 load_chunk(c0, n);
                 forward_chunk(c0, n);
             }
+            // small parameter t's gradient over this chunk alone, added to gS at
+            // the chunk's end: one serial fp32 chain over a 2,048-record episode
+            // left dw2 / db2 (sums of mixed sign) off by 1e-6 of the largest
+            // gradient, 4 to 8 x torch's fp32 error; sums of 64 records, then of
+            // up to 32 chunks, stay at torch's (tests/test_gpu_train_seq.py)
+            float gC = 0.0f;
             if (t < n) {
                 const int s = c0 + t;
                 const float rew = __uint_as_float(a.rec[(size_t)(r0 + s) * 12 + 9]);
@@ -208,9 +214,9 @@ __global__ __launch_bounds__(TR_T) void td0_train_kernel(TrainArgs a) {
             lds_barrier();
             // w2 / b2 gradients from the activations: dw2_u = sum_r dy_r s_ru, db2 = sum_r dy_r
             if (t >= 128 && t < 256) {
-                for (int r = 0; r < n; ++r) gS = fmaf(DY[r], S[r][t - 128], gS);
+                for (int r = 0; r < n; ++r) gC = fmaf(DY[r], S[r][t - 128], gC);
             } else if (t == 256) {
-                for (int r = 0; r < n; ++r) gS += DY[r];
+                for (int r = 0; r < n; ++r) gC += DY[r];
             }
             lds_barrier();
             // dL/dh = ((dy w2) (1 - s)) s  (torch's sigmoid_backward order)
@@ -235,7 +241,8 @@ __global__ __launch_bounds__(TR_T) void td0_train_kernel(TrainArgs a) {
                 }
             }
             if (t < 128)
-                for (int r = 0; r < n; ++r) gS += S[r][t];
+                for (int r = 0; r < n; ++r) gC += S[r][t];
+            gS += gC;
             lds_barrier();
         }
         TSTAMP(3);
