@@ -257,18 +257,29 @@ int bgx_movegen(const uint8_t* d_boards, const uint8_t* d_player, const uint8_t*
         if (int rc = require_domain("bgx_movegen", L.sc, d_boards, d_player, d_dice, n, s)) return rc;
         if (int rc = lease_movegen_space(L.sc)) return rc;
         unsigned* ctr = L.sc->words + 2;   // [0] overflow count, [1] error flags
-        bgx::MovegenArgs a{};
-        a.n_jobs = n;
-        a.in_mode = bgx::IN_U8;
-        a.in_u8 = d_boards;
-        a.in_player = d_player;
-        a.in_dice = d_dice;
-        a.out_mode = bgx::OUT_U8;
-        a.cap = cap;
-        a.out_u8 = d_out_boards;
-        a.out_count = d_out_count;
-        set_fallback(a, ctr, L.sc->ovf, SC_OVF_CAP, L.sc->ws, SC_WS_WAVES, SC_WS_SLOTS, ctr + 1);
-        HIP_TRY(bgx_launch_movegen(&a, s));
+        // The overflow list holds SC_OVF_CAP jobs and every job of a launch may
+        // leave tier 1 (push_ovf drops what does not fit: a dropped job's
+        // out_count would never be written), so a call runs as launches of at
+        // most SC_OVF_CAP jobs each, one after the other on the stream, the
+        // input and output pointers offset. The slices are equal (n / k rounded
+        // up, k the fewest slices that fit), so each holds more than SC_OVF_CAP / 2
+        // jobs and takes the tier-1 kernel the whole call would have taken.
+        const int n_slices = (int)(((int64_t)n + SC_OVF_CAP - 1) / SC_OVF_CAP);
+        const int per = (int)(((int64_t)n + n_slices - 1) / n_slices);
+        for (int j0 = 0; j0 < n; j0 += per) {
+            bgx::MovegenArgs a{};
+            a.n_jobs = n - j0 < per ? n - j0 : per;
+            a.in_mode = bgx::IN_U8;
+            a.in_u8 = d_boards + (size_t)j0 * 52;
+            a.in_player = d_player + j0;
+            a.in_dice = d_dice + (size_t)j0 * 2;
+            a.out_mode = bgx::OUT_U8;
+            a.cap = cap;
+            a.out_u8 = d_out_boards ? d_out_boards + (size_t)j0 * cap * 52 : nullptr;
+            a.out_count = d_out_count + j0;
+            set_fallback(a, ctr, L.sc->ovf, SC_OVF_CAP, L.sc->ws, SC_WS_WAVES, SC_WS_SLOTS, ctr + 1);
+            HIP_TRY(bgx_launch_movegen(&a, s));
+        }
         return BGX_OK;
     });
 }
@@ -620,7 +631,13 @@ int bgx_two_ply_sampled(const bgx_net* net, const uint8_t* d_boards, const uint8
             if (int rc = require_domain("bgx_two_ply", L.sc, d_boards, d_opponent, nullptr, n, s)) return rc;
         }
         const int jobs = n * 21;
-        const int cap = jobs * 768;   // >= any reply count per (board, roll)
+        // 768 rows per (board, roll) job ON AVERAGE, i.e. 21 * 768 = 16,128 per root:
+        // a single list can be far longer (2,140 plays for 1-1 from fifteen
+        // single checkers), but the heaviest root found has 10,839 replies over
+        // the 21 rolls, which leaves room for a workgroup's reserved, unused row
+        // chunks (tests/heavy_cases.py, test_heavy_cases.py); beyond it the call
+        // fails with BGX_E_CAPACITY
+        const int cap = jobs * 768;
         DevBuf<uint32_t> reply;
         DevBuf<int32_t> off, cnt;
         DevBuf<float> V, jv, zt;

@@ -6,7 +6,8 @@
 // buffers under AddressSanitizer. Writes every job's record count and rows
 // (in order) to the dump file, so two launch forms (BGX_REPLY_DBL=0 / 1) can be
 // compared byte for byte.
-// Usage: reply_emu positions.bin n_roots dump.bin   (positions: 8 packed words + mover, int32)
+// Usage: reply_emu positions.bin n_roots dump.bin [cap_rows]   (positions: 8 packed words + mover, int32;
+// cap_rows: the flat output's rows, default 64 per job + 4096)
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -31,7 +32,7 @@ int main(int argc, char** argv) {
         fclose(f);
     }
     const int n = (int)rows.size() / 8;
-    const int n_jobs = n * 21, cap = n * 21 * 64 + 4096;
+    const int n_jobs = n * 21, cap = argc > 4 ? atoi(argv[4]) : n * 21 * 64 + 4096;
     const int ws_waves = 64, ws_slots = 16384, ovf_cap = 1 << 16;
     std::vector<uint32_t> out((size_t)cap * 8, 0xDEADBEEFu), ws((size_t)ws_waves * 5 * ws_slots, 0u);
     std::vector<int32_t> off(n_jobs, -7), cnt(n_jobs, -7), ovf(ovf_cap, 0);
@@ -59,8 +60,15 @@ int main(int argc, char** argv) {
     // job_off / job_cnt start poisoned (-7): every job of the launch must write both
     int unwritten = 0;
     for (int j = 0; j < n_jobs; ++j) unwritten += off[j] == -7 || cnt[j] == -7;
-    printf("{\"roots\": %d, \"rows\": %u, \"tier2_jobs\": %u, \"flags\": %u, \"unwritten_jobs\": %d}\n", n, ctr[0],
-           ctr[2], ctr[3], unwritten);
+    // the tier-3 workspace starts zeroed: a block that ran a job there (run_global) left words in its slice
+    int tier3_slices = 0;
+    for (int w = 0; w < ws_waves; ++w) {
+        bool touched = false;
+        for (size_t k = 0; k < (size_t)5 * ws_slots && !touched; ++k) touched = ws[(size_t)w * 5 * ws_slots + k] != 0u;
+        tier3_slices += touched;
+    }
+    printf("{\"roots\": %d, \"rows\": %u, \"tier2_jobs\": %u, \"flags\": %u, \"unwritten_jobs\": %d, "
+           "\"tier3_slices\": %d}\n", n, ctr[0], ctr[2], ctr[3], unwritten, tier3_slices);
     FILE* f = fopen(argv[3], "wb");
     if (!f) return 2;
     for (int j = 0; j < n_jobs; ++j) {

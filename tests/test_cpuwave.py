@@ -15,6 +15,7 @@ slice and must leave the parent map zero. Random positions (bar 0-2, borne-off
 checkers). The 3,650 positions of tests/test_gpu_reply.py passed the same
 check (tools: `dbl_check 4000 1 positions.bin`, ~9 min).
 """
+import json
 import os
 import shutil
 import subprocess
@@ -85,15 +86,17 @@ def _unpack(w):
     return out
 
 
-def _reply_vs_oracle(tmp_path, defs, n_cu=2):
+def _reply_vs_oracle(tmp_path, defs, n_cu=2, pos=None, cap=None):
     """The reply launch emulated (per-roll doubles items and the board-major
     doubles kernel, BGX_REPLY_DBL=0 / 1, the latter with half its rows in
     per-roll items, BGX_REPLY_DBL_TAIL=32; extra defs) on self-play and random
     positions over n_cu emulated CUs: both kernels' per-job output
-    byte-identical, and every (board, roll) list the oracle's, order included."""
+    byte-identical, and every (board, roll) list the oracle's, order included.
+    pos: other (board, opponent) roots; cap: the flat output's rows."""
     orc = pytest.importorskip("oracle")
     from test_gpu_parity import _fuzz_positions, _random_positions
-    pos = _fuzz_positions(11, 4) + _random_positions(12, 90)
+    if pos is None:
+        pos = _fuzz_positions(11, 4) + _random_positions(12, 90)
     boards = np.stack([p[0] for p in pos])
     opp = np.array([p[1] for p in pos], np.uint8)
     rows = np.zeros((len(pos), 9), np.uint32)
@@ -101,16 +104,17 @@ def _reply_vs_oracle(tmp_path, defs, n_cu=2):
     rows[:, 8] = opp
     pfile = tmp_path / "pos.bin"
     rows.tofile(pfile)
-    dumps = []
+    dumps, reports = [], []
     exe = _build(tmp_path, "reply_emu.cpp", "reply_emu", list(defs))
     for v in ("0", "1"):
         env = {**os.environ, "ASAN_OPTIONS": "verify_asan_link_order=0:detect_leaks=0", "EMU_N_CU": str(n_cu),
                "BGX_REPLY_DBL": v, "BGX_REPLY_DBL_TAIL": "32"}
         dump = tmp_path / ("dump" + v + ".bin")
-        r = subprocess.run([str(exe), str(pfile), str(len(pos)), str(dump)], capture_output=True, text=True,
-                           timeout=900, env=env)
+        r = subprocess.run([str(exe), str(pfile), str(len(pos)), str(dump)] + ([str(cap)] if cap else []),
+                           capture_output=True, text=True, timeout=900, env=env)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
         dumps.append(dump.read_bytes())
+        reports.append(r.stdout)
     assert dumps[0] == dumps[1]
     d = np.frombuffer(dumps[0], np.int32)
     at = 0
@@ -125,6 +129,7 @@ def _reply_vs_oracle(tmp_path, defs, n_cu=2):
             assert c == n, (i, a, b, c, n)
             np.testing.assert_array_equal(got, res[:n], err_msg=f"board {i} roll {a}-{b}")
     assert at == d.shape[0]
+    return reports
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")
@@ -150,6 +155,33 @@ def test_reply_launch_emulated_with_subqueue_equals_oracle(tmp_path):
     exit test once split waves (round 4: 11-27 wrong late-row lists per 76,650
     at 256 CUs; the exit verdict is now lane 0's, broadcast)."""
     _reply_vs_oracle(tmp_path, [], n_cu=64)
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")
+def test_reply_launch_emulated_on_heavy_roots_equals_oracle(tmp_path):
+    """The heaviest legal positions (tests/heavy_cases.py) as reply roots, the
+    mover as the opponent who replies: lists of up to 2,140 plays leave the
+    reply kernel's tier 1 for the block kernel, whose coop_doubles gives up
+    above 2,048 entries a level and hands the job to run_global on the
+    workspace -- the tier-1 -> tier-2 -> tier-3 path, under
+    AddressSanitizer, both BGX_REPLY_DBL arms, two emulated CUs, with the rows
+    bgx_two_ply allocates (21 x 768 per root). Every (board, roll) list equals
+    the oracle's, order included."""
+    import heavy_cases as hc
+    pos = [(b, pl) for _, b, pl in hc.cases()]
+    orc = pytest.importorskip("oracle")
+    reports = _reply_vs_oracle(tmp_path, [], n_cu=2, pos=pos, cap=len(pos) * 21 * 768)
+    # Which jobs leave tier 1 depends on their level-1..3 lists, not on the final
+    # count (path doubles stream their leaves): the four 1-1 jobs of 2,140 plays
+    # have 561 three-move partial plays, above tier 1's 480 entries, and a list
+    # above K_F = 2,048 cannot end in tier 2, so they ran in the block kernel and
+    # then on a workspace slice.
+    over = sum(orc.movegen(b, pl, d, d, cap=1)[0] > hc.T2_PARENTS for b, pl in pos for d in range(1, 7))
+    assert over == 4
+    for rep in reports:
+        st = json.loads(rep.strip().splitlines()[-1])
+        assert st["tier2_jobs"] >= over and st["tier3_slices"] >= 1, st
+        assert st["flags"] == 0 and st["unwritten_jobs"] == 0, st
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")

@@ -41,7 +41,7 @@ def _collect(e, steps, chunk=100):
     return hdrs, recs
 
 
-def _check_transitions(weights, hdrs, recs, ply):
+def _check_transitions(weights, hdrs, recs, ply, max_steps=300):
     """Every record against the oracle: afterstate, V(s) / V(a), reward, done,
     win type, shaping; the 198-d observation (mover's indicator) and
     next_observation (the next player's, or the winner's at a terminal step,
@@ -100,8 +100,8 @@ def _check_transitions(weights, hdrs, recs, ply):
                     assert int(row[4]) == int(d["step"][last]) + 1
                     assert int(row[5]) & 0xFF == int(d["win_type"][last])
                     assert (int(row[5]) >> 8) & 0xFF == int(d["mover"][last])
-            assert int(row[4]) <= 300
-            assert int(row[4]) == 300 or (n > 0 and d["done"][o + n - 1])
+            assert int(row[4]) <= max_steps
+            assert int(row[4]) == max_steps or (n > 0 and d["done"][o + n - 1])
             o += n
     return n_checked
 

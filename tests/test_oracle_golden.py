@@ -39,6 +39,27 @@ def test_movegen_digests():
         assert hashlib.sha256(res.tobytes()).digest() == g["sha256"][i].tobytes(), i
 
 
+def test_movegen_heavy_digests():
+    """The heaviest legal positions (tests/heavy_cases.py, lists up to 2,140
+    plays), all 36 rolls: the reference's count and ordered boards, and for the
+    three largest lists the plays' sub-move counts."""
+    import heavy_cases as hc
+    g = golden("movegen_heavy.npz")
+    cs = hc.cases()
+    assert len(g["boards"]) == 36 * len(cs) and g["count"].max() == 2140
+    for i in range(len(g["boards"])):
+        name, b, pl = cs[i // 36]
+        assert g["name"][i] == name and g["player"][i] == pl and tuple(g["dice"][i]) == hc.ROLLS36[i % 36]
+        np.testing.assert_array_equal(g["boards"][i], b)
+        n, res, nsub = orc.movegen(b, pl, *g["dice"][i])
+        assert n == g["count"][i], (name, i)
+        assert hashlib.sha256(res.tobytes()).digest() == g["sha256"][i].tobytes(), (name, i)
+        for k, j in enumerate(g["nsub_job"]):
+            if j == i:
+                np.testing.assert_array_equal(nsub, g["nsub"][g["nsub_offsets"][k]:g["nsub_offsets"][k + 1]])
+    assert len(g["nsub_job"]) == 3 and (g["count"][g["nsub_job"]] >= 2140).all()
+
+
 def test_encode_live_and_interleaved_bit_exact():
     e = golden("encode.npz")
     live = orc.encode_many(e["boards"], e["player"], 0)

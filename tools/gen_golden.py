@@ -4,6 +4,7 @@
 Run in the build container only (the reference is not on the GPU box):
 
     PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py
+    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py --only heavy   # movegen_heavy.npz alone
 
 What is imported from /root/reference (read-only; nothing is copied):
   * src.backgammon.get_all_possible_moves   (moves/generate_all_moves.py:7-66)
@@ -841,6 +842,32 @@ def main_trainer(n_eps=200):
     print(f"[gen] trainer: {n_eps} episodes, {first} records; loss {out['metric_loss']:.6g}", flush=True)
 
 
+def main_heavy():
+    """tests/golden/movegen_heavy.npz: the reference's lists on the heaviest legal
+    positions (tests/heavy_cases.py), all 36 rolls of every member as count +
+    sha256 of the ordered result boards; for the three largest lists also the
+    plays' sub-move counts (nsub)."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import heavy_cases
+    t0 = time.time()
+    names, bo, pl_, dice, cnt, dg, nsubs = [], [], [], [], [], [], {}
+    for name, b, pl in heavy_cases.cases():
+        for d0, d1 in heavy_cases.ROLLS36:
+            boards, nsub, _ = ref_moves(b, pl, d0, d1)
+            names.append(name); bo.append(b); pl_.append(pl); dice.append((d0, d1))
+            cnt.append(len(boards)); dg.append(digest(boards))
+            nsubs[len(names) - 1] = np.array(nsub, np.uint8)
+    top = sorted(range(len(cnt)), key=lambda i: (-cnt[i], i))[:3]
+    np.savez_compressed(os.path.join(OUT, "movegen_heavy.npz"), name=np.array(names), boards=np.stack(bo),
+                        player=np.array(pl_, np.uint8), dice=np.array(dice, np.uint8),
+                        count=np.array(cnt, np.int32), sha256=np.stack(dg),
+                        nsub_job=np.array(top, np.int32),
+                        nsub_offsets=np.cumsum([0] + [cnt[i] for i in top]).astype(np.int64),
+                        nsub=np.concatenate([nsubs[i] for i in top]))
+    print(f"[gen] movegen_heavy: {len(cnt)} jobs, largest list {max(cnt)}, nsub for jobs {top} "
+          f"({time.time() - t0:.1f}s)", flush=True)
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["--only", "two_ply"]:
         main_two_ply()
@@ -848,5 +875,7 @@ if __name__ == "__main__":
         main_env()
     elif sys.argv[1:] == ["--only", "trainer"]:
         main_trainer()
+    elif sys.argv[1:] == ["--only", "heavy"]:
+        main_heavy()
     else:
         main()
