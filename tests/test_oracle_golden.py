@@ -78,15 +78,98 @@ def test_value_within_1e5(which, weights_seed0, weights_ckpt):
     assert np.max(np.abs(got - ref)) < 1e-5
 
 
+def _outcome_cells(o):
+    """Every named cell of the outcome rules occurs in outcomes.npz with the
+    reference's label, read off the fixture's arrays alone (the boards are
+    parsed by outcome_cases.features, in the mover's view: the mover runs
+    towards point 23, home 18..23, "behind a run" = on a higher point)."""
+    import outcome_cases as oc
+    boards, player = o["boards"], o["player"]
+    # each board twice: with the player who moved, then with the other one
+    np.testing.assert_array_equal(boards[0::2], boards[1::2])
+    assert (player[0::2] != player[1::2]).all()
+    assert not o["prime"][1::2].any() and not o["closed_out"][1::2].any()
+    assert not (o["game_over"][1::2] & (boards[1::2, 50:52].max(axis=1) < 15)).any()
+    for pl in (0, 1):
+        idx = [i for i in range(0, len(boards), 2) if player[i] == pl]
+        F = {i: oc.features(boards[i], pl) for i in idx}
+
+        def cell(cond, key, want, what):
+            hit = [i for i in idx if cond(F[i])]
+            assert hit, (pl, what)
+            bad = [i for i in hit if bool(o[key][i]) != want]
+            assert not bad, (pl, what, boards[bad[0]])
+            return hit
+
+        one = lambda f: f["n_theirs"] == 1 and f["bar_o"] == 0 and f["max_stack"] == 2  # noqa: E731
+        for n in (5, 6, 7):
+            run = lambda f: f["run_len"] == n and f["n_made"] == n  # noqa: E731
+            assert {F[i]["run_start"] for i in idx if run(F[i])} == set(range(25 - n)), (pl, n)
+            cell(lambda f: run(f) and one(f) and f["first_behind"], "prime", True, f"run {n}, first point behind")
+            cell(lambda f: run(f) and one(f) and f["theirs"][23] and f["run_end"] < 22, "prime", True,
+                 f"run {n}, farthest point behind")
+            cell(lambda f: run(f) and one(f) and f["ahead"], "prime", False, f"run {n}, only ahead")
+            cell(lambda f: run(f) and one(f) and f["theirs"][max(f["run_start"] - 1, 0)] and f["run_start"] > 0,
+                 "prime", False, f"run {n}, first point ahead")
+            cell(lambda f: run(f) and f["n_theirs"] == 0 and f["bar_o"] == 1, "prime", False, f"run {n}, only the bar")
+            cell(lambda f: run(f) and f["n_theirs"] == 0 and f["off_o"] == 15, "prime", False, f"run {n}, all off")
+            edge = cell(lambda f: run(f) and f["run_end"] == 23, "prime", False, f"run {n} against the edge")
+            assert len(edge) >= 19 - n                       # every free point, the bar, all off
+            for s in range(25 - n):                          # one checker on every free point in turn
+                pts = {int(np.flatnonzero(F[i]["theirs"])[0]) for i in idx
+                       if run(F[i]) and one(F[i]) and F[i]["run_start"] == s and F[i]["mine"].sum() == 2 * n}
+                assert pts == set(range(24)) - set(range(s, s + n)), (pl, n, s)
+            cell(lambda f: run(f) and f["max_stack"] == 3 and f["first_behind"], "prime", True, f"run {n}, spare on it")
+            cell(lambda f: run(f) and one(f) and f["mine"].sum() == 2 * n + 1 and f["first_behind"], "prime", True,
+                 f"run {n}, spare elsewhere")
+        cell(lambda f: f["run_len"] == 5 and f["max_stack"] == 7 and f["first_behind"], "prime", True, "stack of 7")
+        behind = lambda f: f["first_behind"] or f["far_behind"]  # noqa: E731
+        cell(lambda f: f["run_len"] == 4 and f["n_made"] == 4 and f["first_behind"], "prime", False, "run of 4")
+        cell(lambda f: f["run_len"] == 4 and f["n_made"] == 4 and f["far_behind"], "prime", False, "run of 4")
+        single = cell(lambda f: f["n_made"] == 4 and (f["mine"] == 1).sum() == 1 and f["run_len"] < 5 and (
+            lambda occ: any(occ[s:s + 5].all() for s in range(20)))(f["mine"] > 0) and behind(f), "prime", False,
+            "run of 5 with a single checker")
+        assert {F[i]["run_len"] for i in single} == {2, 3, 4}   # the single checker at the ends and inside
+        cell(lambda f: f["n_made"] == 7 and f["run_len"] == 4 and behind(f), "prime", False, "4 + gap + 3")
+        for k in range(8, 16):
+            cell(lambda f: f["max_stack"] == k, "prime", False, f"stack of {k}")
+        for base in (18, 17):
+            for h in range(base, base + 6):
+                for v in (0, 1, 2, 5):
+                    for bar in (0, 1, 2, 15):
+                        cell(lambda f: f["mine"][h] == v and f["bar_o"] == bar and f["mine"].sum() == 10 + v
+                             and (np.delete(f["mine"][base:base + 6], h - base) == 2).all(),
+                             "closed_out", base == 18 and v >= 2 and bar > 0, f"close-out {base} {h} {v} {bar}")
+        for off in (0, 1, 14):
+            for bar in (0, 1):
+                for pt in [None] + list(range(24)):
+                    if off + bar + (pt is not None) > 15:
+                        continue
+                    hit = cell(lambda f: f["off_m"] == 15 and f["off_o"] == off and f["bar_o"] == bar and f["n_theirs"] == (
+                        pt is not None) and (pt is None or f["theirs"][pt] == 1), "game_over", True, f"over {off} {bar} {pt}")
+                    for i in hit:
+                        assert bool(o["gammon"][i]) == (off == 0)
+                        assert bool(o["backgammon"][i]) == (off == 0 and (bar > 0 or (pt is not None and pt >= 18)))
+
+
 def test_reward_predicates():
-    p = golden("predicates.npz")
     names = {"game_over": "check_game_over", "gammon": "check_for_gammon",
              "backgammon": "check_for_backgammon", "prime": "made_at_least_five_prime",
              "closed_out": "is_closed_out"}
-    for key, fn in names.items():
-        got = np.array([orc.predicate(fn, b, pl) for b, pl in zip(p["boards"], p["player"])])
-        np.testing.assert_array_equal(got, p[key], err_msg=key)
-    assert p["prime"].any() and p["closed_out"].any() and p["backgammon"].any()
+    for fixture in ("predicates.npz", "outcomes.npz"):
+        p = golden(fixture)
+        for key, fn in names.items():
+            got = np.array([orc.predicate(fn, b, pl) for b, pl in zip(p["boards"], p["player"])])
+            np.testing.assert_array_equal(got, p[key], err_msg=fixture + " " + key)
+        assert p["prime"].any() and p["closed_out"].any() and p["backgammon"].any()
+    # outcomes.npz: the enumerated boards of tests/outcome_cases.py, and every
+    # named cell of the rules with the reference's label
+    import outcome_cases as oc
+    o = golden("outcomes.npz")
+    boards, player, _ = oc.fixture_rows()
+    np.testing.assert_array_equal(o["boards"], boards)
+    np.testing.assert_array_equal(o["player"], player)
+    _outcome_cells(o)
 
 
 def test_env_greedy_trajectories():

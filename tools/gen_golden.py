@@ -5,6 +5,7 @@ Run in the build container only (the reference is not on the GPU box):
 
     PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py
     PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py --only heavy   # movegen_heavy.npz alone
+    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py --only outcomes   # outcomes.npz alone
 
 What is imported from /root/reference (read-only; nothing is copied):
   * src.backgammon.get_all_possible_moves   (moves/generate_all_moves.py:7-66)
@@ -868,8 +869,33 @@ def main_heavy():
           f"({time.time() - t0:.1f}s)", flush=True)
 
 
+def main_outcomes():
+    """tests/golden/outcomes.npz: the reference's five reward predicates
+    (env_helper.py:113-242) on the enumerated after-move boards of
+    tests/outcome_cases.py, each board with the player who moved and with the
+    other one; the arrays of predicates.npz."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import outcome_cases
+    t0 = time.time()
+    boards, player, _ = outcome_cases.fixture_rows()
+    fns = {"game_over": env_helper.check_game_over, "gammon": env_helper.check_for_gammon,
+           "backgammon": env_helper.check_for_backgammon, "prime": env_helper.made_at_least_five_prime,
+           "closed_out": env_helper.is_closed_out}
+    preds = {k: [] for k in fns}
+    for b, p in zip(boards, player):
+        ib = to_ib(b)
+        for k, fn in fns.items():
+            preds[k].append(bool(fn(ib, Player(int(p)))))
+    np.savez_compressed(os.path.join(OUT, "outcomes.npz"), boards=boards, player=player,
+                        **{k: np.array(v, bool) for k, v in preds.items()})
+    print(f"[gen] outcomes: {len(boards)} rows, prime {sum(preds['prime'])}, closed out {sum(preds['closed_out'])}, "
+          f"game over {sum(preds['game_over'])} ({time.time() - t0:.1f}s)", flush=True)
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["--only", "two_ply"]:
+    if sys.argv[1:] == ["--only", "outcomes"]:
+        main_outcomes()
+    elif sys.argv[1:] == ["--only", "two_ply"]:
         main_two_ply()
     elif sys.argv[1:] == ["--only", "env"]:
         main_env()
