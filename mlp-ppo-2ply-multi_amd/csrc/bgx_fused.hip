@@ -22,11 +22,17 @@
 //      after a move), into a slot per lane in LDS (DrawSlot, bgx_engine.h).
 //      The choice items read their lanes' slots and evaluate Philox
 //      themselves only past them (new_game, the roll after a truncation). A
-//      choice waits for the tiles holding its lanes' rows, a job for its
-//      lane's choice, the draw item for every lane's choice (LDS flags); the
-//      MFMA-bound tiles, the latency-bound choices and the issue-bound
-//      movegen jobs share the SIMDs, and the draws are made by a wave that
-//      would otherwise sit in the step's end barrier.
+//      choice waits for the tiles holding its lanes' rows (an LDS flag per
+//      tile). A lane's choice publishes the lane in the step's LDS bitmasks
+//      (bgx_claim.h: bit v = lane v in the words open | stepped and
+//      dbl | rule, the class bits computed once, from the registers holding
+//      the lane's new state); a job item reads the masks in one LDS read,
+//      picks the lowest open lane in scalar code (doubles first) and claims
+//      it with one fetch-and on the open bits, a pairable lane a second one
+//      the same way; the draw item waits until the stepped bits cover the
+//      step's lanes. The MFMA-bound tiles, the latency-bound choices and the
+//      issue-bound movegen jobs share the SIMDs, and the draws are made by a
+//      wave that would otherwise sit in the step's end barrier.
 // Replaces, per lane and step, Worker.play_episode's inner loop
 // (src/multi/worker.py:101-162) over BackgammonEnv.step / update_legal_moves
 // (src/environments/backgammon_env.py:130-308) and the policy forward
@@ -40,6 +46,8 @@
 #include "bgx_engine.h"
 #include "bgx_mlp.h"
 #include "bgx_movegen.h"
+#define BGX_CLAIM_FN BGX_DEV
+#include "bgx_claim.h"
 
 namespace bgx {
 
@@ -62,10 +70,8 @@ template <int FL> struct FusedTail {
     int cnt[FL];                    // lane's full candidate count this step (-1: redo in tier 2)
     int go[2];                      // step s runs iff go[s & 1] (the balanced launch's tickets)
     int qn[2];                      // the step queue's item counters (by pass parity)
-    int ncl;                        // lanes whose next tier-1 job is claimed this step (pipelined queue)
+    ClaimWords cw;                  // this step's lane masks: open | stepped, dbl | rule (bgx_claim.h; zero at the queue's opening barrier)
     unsigned tdone[64];             // MLP tile t of this step is written iff tdone[t] == the step's tag
-    unsigned chosen[FL];            // lane v of this step is stepped iff chosen[v] == the step's tag
-    unsigned claim[FL];             // lane v's next tier-1 job is taken iff claim[v] == the step's tag
     int pre[FL + 1];                // MLP row prefix over the lanes
     uint32_t job[FL][8];            // the lanes' jobs: packed board words 0..6, player | d0 << 8 | d1 << 16
     DrawSlot draw[FL];              // the lanes' Philox draws for their next step (the draw item, bgx_engine.h)
@@ -106,6 +112,55 @@ __device__ __forceinline__ const FusedArgs& launch_args() {
     asm volatile("" : "+s"(p));
     return *(const FusedArgs*)p;
 }
+// The claim protocol's operations on the LDS mask words (bgx_claim.h), for a
+// whole wave: loads are made by every thread (one address: a broadcast) and
+// made uniform with readfirstlane, so the candidate selection behind them is
+// scalar code; a fetch-and is made by lane 0 and its result broadcast. The
+// publisher's ORs belong to the calling thread (a half-wave's lead).
+struct WaveClaimOps {
+    int l;   // the calling thread's lane
+    static __device__ __forceinline__ unsigned long long uni64(unsigned long long x) {
+        const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
+        const uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(x >> 32));
+        return (unsigned long long)a | ((unsigned long long)b << 32);
+    }
+    __device__ __forceinline__ unsigned long long load(const unsigned long long* p) const {
+        return uni64(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+    }
+    // one poll: both words in one 128-bit LDS read
+    __device__ __forceinline__ void load2(const ClaimWords& W, unsigned long long& so, unsigned long long& cls) const {
+        typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+        const v4u r = *(const volatile __attribute__((address_space(3))) v4u*)(const void*)&W;
+        so = uni64((unsigned long long)r.x | ((unsigned long long)r.y << 32));
+        cls = uni64((unsigned long long)r.z | ((unsigned long long)r.w << 32));
+    }
+    __device__ __forceinline__ unsigned long long fetch_and(unsigned long long* p, unsigned long long m) const {
+        unsigned long long old = 0ull;
+        if (l == 0) old = __hip_atomic_fetch_and(p, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        return uni64(old);
+    }
+    __device__ __forceinline__ void or_relaxed(unsigned long long* p, unsigned long long m) const {
+        __hip_atomic_fetch_or(p, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __device__ __forceinline__ void or_release(unsigned long long* p, unsigned long long m) const {
+        __hip_atomic_fetch_or(p, m, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __device__ __forceinline__ void acquire() const { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); }
+    __device__ __forceinline__ void relax() const { __builtin_amdgcn_s_sleep(1); }
+};
+// nd_by_rule of a lane's position from a state held in registers: the root's
+// fields the rule reads, picked by selects (make_root indexes the board words
+// by the player, which would put the state on the stack)
+__device__ __forceinline__ bool lane_by_rule(const LaneState& s) {
+    const bool p1 = s.p != 0;
+    Root R{};
+    R.player = s.p;
+    R.m0 = p1 ? s.w[3] : s.w[0];
+    R.m2 = p1 ? s.w[5] : s.w[2];
+    R.bar = (p1 ? s.w[6] >> 4 : s.w[6]) & 15u;
+    R.off = (p1 ? s.w[6] >> 12 : s.w[6] >> 8) & 15u;
+    return nd_by_rule(R);
+}
 // the movegen's view of them (slot output into the lanes' candidate rows)
 __device__ __forceinline__ MovegenArgs job_args(const FusedArgs& f) {
     MovegenArgs a{};
@@ -144,7 +199,6 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
         for (int i = t; i < 128; i += NT) T.w2s[i] = f.rowc[i];
     }
     for (int i = t; i < 64; i += NT) T.tdone[i] = 0u;
-    for (int i = t; i < FL; i += NT) T.chosen[i] = T.claim[i] = 0u;
     unsigned qtag = 0u;   // this workgroup's step counter (tags the flags; never 0 on a live step)
     // split-fp16 W fragments, loaded once, global -> LDS by LDS-DMA (every load
     // of a wave in flight at once; the prologue's lane loads overlap them)
@@ -177,6 +231,9 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
     // of them that saw a second such lane ready and unclaimed; clocks / count
     // of the pair items (two jobs each)
     unsigned long long tpr[7] = {0, 0, 0, 0, 0, 0, 0};
+    // waits, every wave: the choice items' tile wait, the job items' claim
+    // (polls and fetch-ands), the step's end barrier
+    unsigned long long twt[3] = {0, 0, 0};
     constexpr bool prof = PROF;
     auto tick = [&](int k) {
         if (prof && t == 0) {
@@ -191,18 +248,33 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
     // choice item waits (LDS flags, bounded) for the tiles holding its lanes'
     // rows; a tier-1 job item waits for a stepped, unclaimed lane. Every item a
     // waiting item needs is handed out before it, and tiles wait on nothing, so
-    // the waits end. A job item that claimed a rule-mode non-doubles lane
-    // claims one more such lane when one is ready at that moment (never waiting
-    // for one) and expands both in one pass, so job items can outnumber the
-    // lanes left: claims only grow and T.ncl counts them, every lane's choice
-    // is handed out before any job item, and a job item either claims a lane,
-    // or sees all of the step's lanes claimed and ends as a no-op, or reaches
-    // the poll bound (BGX_ERRF_WAIT_BOUND).
+    // the waits end. The lanes' progress is two 64-bit mask words (T.cw,
+    // bgx_claim.h), zeroed by thread 0 in front of the queue's opening barrier:
+    // open | stepped << 32 and dbl | rule << 32, bit v = lane v. A choice
+    // item's lead threads write their lanes' new state and OR its class bits
+    // (from the registers holding the state), then, behind the release fence,
+    // set the lane's open and stepped bits with one 64-bit OR (release): a
+    // reader that sees the lane open sees its state; a class bit it misses
+    // costs only the hint. A job item reads both words in one LDS read made
+    // uniform, picks the lowest open doubles lane, else the lowest open lane,
+    // in scalar code, and claims it with one fetch-and by lane 0 that clears
+    // the open bit: won iff the returned word had it, and a loss retries at
+    // once from that word. A job item that claimed a pairable (rule-mode
+    // non-doubles) lane claims one more such lane when one is open at that
+    // moment, from the word its claim returned (at most two more fetch-ands,
+    // never waiting for one) and expands both in one pass, so job items can
+    // outnumber the lanes left: a claimed lane never reopens, every lane's
+    // choice is handed out before any job item, and a job item either claims a
+    // lane, or sees (one atomic load) every lane of the step stepped and none
+    // open and ends as a no-op, or reaches the poll bound
+    // (BGX_ERRF_WAIT_BOUND). The non-pipelined queues (step -1, steps without
+    // choices, the three-pass form) deal the jobs statically and leave the
+    // masks zero.
     // The queue's last item, the draw item, draws the next step's Philox
     // numbers of every lane (T.draw) and first waits, in the pipelined queue,
-    // until every lane of the step is stepped (T.chosen): a lane's counter is
-    // final only behind its own choice. It is handed out after every choice
-    // and every job item, the choices wait for tiles only and tiles for
+    // until the stepped bits cover the step's lanes (one word per poll): a
+    // lane's counter is final only behind its own choice. It is handed out
+    // after every choice and every job item, the choices wait for tiles only and tiles for
     // nothing, so its wait ends as theirs do (same bound, same flag); no item
     // waits for it: the step's end barrier publishes the slots. Step -1's
     // queue has one too (the launch's first step), with nothing to wait for,
@@ -346,7 +418,8 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
             if (t == 0) {
                 T.qn[0] = NW;
                 T.qn[1] = NW;
-                T.ncl = 0;
+                T.cw.so = 0ull;
+                T.cw.cls = 0ull;
             }
             ++qtag;
             M1.map[l] = 0u;   // (tier 2 may have used the scratch)
@@ -435,15 +508,18 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                         const FusedArgs& f = launch_args();
                         const EngineDev& e = f.e;
                         if (pipelined) {
+                            const unsigned long long w0 = prof ? wall_clock64() : 0ull;
                             const int va = lo + 2 * p, vb = lo + 2 * p + 2 < hi ? lo + 2 * p + 2 : hi;
                             const int r0 = T.pre[va], r1 = T.pre[vb];   // the pair's rows [r0, r1)
                             if (r1 > r0) {
                                 for (int tt = r0 >> 5; tt <= (r1 - 1) >> 5; ++tt) wait_flag(&T.tdone[tt]);
                                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                             }
+                            if (prof) twt[0] += wall_clock64() - w0;
                         }
                         const int v = lo + 2 * p + (l >> 5);
                         const bool lead = (l & 31) == 0;
+                        const WaveClaimOps cops{l};
                         if (v < hi) {
                             const int i = g * FL + v;
                             const unsigned long long s1 = prof ? wall_clock64() : 0ull;
@@ -490,12 +566,21 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                                 }
                             }
                             wave_sync();
-                            if (lead) T.st[v] = sr;
+                            if (lead) {
+                                T.st[v] = sr;
+                                // the class of the lane's next job, from the registers
+                                // that hold its new state: its bits go out beside the
+                                // state, in front of the release
+                                if (pipelined)
+                                    claim_publish_class(cops, T.cw, v, sr.d0 == sr.d1,
+                                                        PAIR && sr.d0 != sr.d1 && lane_by_rule(sr));
+                            }
                             if (prof) tw[3] += wall_clock64() - s1;
                         }
+                        // the lane's state and class bits before its open and stepped
+                        // bits (one 64-bit OR, release; bgx_claim.h)
                         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                        if (lead && v < hi)
-                            __hip_atomic_store(&T.chosen[v], qtag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        if (pipelined && lead && v < hi) claim_publish_open(cops, T.cw, v);
                     } else if (it < qt + qp + qj) {
                         // ---- 1. a tier-1 job of the next step in this wave's slice:
                         // lane order behind the choices (a lane's job waits for its
@@ -507,76 +592,33 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                         const bool k_pair = f.pair != 0;
                         int v, v2 = -1;   // the item's lane; the lane paired with it (or none)
                         if (pipelined) {
-                            // the first stepped and unclaimed lane, doubles (the long
-                            // jobs) first. Every lane's choice was handed out before
-                            // any job item and claims only grow (T.ncl counts them), so
-                            // an item either claims a lane, or sees every lane claimed
-                            // (pairs leave items over: a no-op), or reaches the bound.
-                            v = -1;
-                            for (unsigned spin = 0; v < 0; ++spin) {
-                                const bool ready =
-                                    act(l) &&
-                                    __hip_atomic_load(&T.chosen[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == qtag &&
-                                    __hip_atomic_load(&T.claim[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != qtag;
-                                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                                const bool isd = ready && T.st[l].d0 == T.st[l].d1;
-                                const uint32_t md = (uint32_t)ballot(isd), mo = (uint32_t)ballot(ready && !isd);
-                                if (md | mo) {
-                                    const int cand = md ? __ffs(md) - 1 : __ffs(mo) - 1;
-                                    int won = 0;
-                                    if (l == 0) {
-                                        const unsigned old = T.claim[cand];
-                                        won = old != qtag && atomicCAS(&T.claim[cand], old, qtag) == old;
-                                        if (PAIR && won) atomicAdd(&T.ncl, 1);
-                                    }
-                                    if (uniform(won)) v = cand;
-                                    if (prof && v >= 0) tpr[2] += 1;
-                                } else {
-                                    // every lane claimed: an item left over by the pairs
-                                    if (PAIR &&
-                                        uniform(__hip_atomic_load(&T.ncl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) >= nj)
-                                        break;
-                                    if (spin >= (1u << 24)) {   // bounded
-                                        if (l == 0) atomicOr(a.err_flags, BGX_ERRF_WAIT_BOUND);
-                                        v = kj;
-                                        break;
-                                    }
-                                    __builtin_amdgcn_s_sleep(1);
-                                }
+                            // the lowest open lane of the step's masks, doubles (the
+                            // long jobs) first, by one fetch-and on the open bits
+                            // (claim_take, bgx_claim.h). Every lane's choice was
+                            // handed out before any job item and a claimed lane never
+                            // reopens, so an item either claims a lane, or sees every
+                            // lane stepped and none open (pairs leave items over: a
+                            // no-op, v < 0), or reaches the bound. A pairable lane
+                            // takes one more pairable lane that is open at that
+                            // moment, from the word its claim returned: at most two
+                            // more fetch-ands, never a wait, no lane state read.
+                            const unsigned long long c0 = prof ? wall_clock64() : 0ull;
+                            const WaveClaimOps cops{l};
+                            const Claim cl = claim_take<PAIR>(cops, T.cw, claim_range(lo, hi), k_pair, prof);
+                            v = cl.v;
+                            v2 = cl.v2;
+                            if (cl.flags & CLAIM_BOUND) {   // bounded
+                                if (l == 0) atomicOr(a.err_flags, BGX_ERRF_WAIT_BOUND);
+                                v = kj;
+                            }
+                            if (prof) {
+                                twt[1] += wall_clock64() - c0;
+                                if (cl.v >= 0) tpr[2] += 1;
+                                if (cl.flags & CLAIM_RULE) tpr[3] += 1;
+                                if (cl.flags & CLAIM_PARTNER) tpr[4] += 1;
                             }
                         } else {
                             v = kj < nd ? select_bit(dmask, kj) : select_bit(omask, kj - nd);
-                        }
-                        if (PAIR && pipelined && v >= 0 && (k_pair || prof) && T.st[v].d0 != T.st[v].d1) {
-                            // a rule-mode non-doubles lane (pairable: T.st) takes one more
-                            // such lane, ready and unclaimed now, with the same
-                            // compare-and-swap: two attempts, no waiting
-                            const bool free_l =
-                                act(l) &&
-                                __hip_atomic_load(&T.chosen[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == qtag &&
-                                __hip_atomic_load(&T.claim[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != qtag;
-                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                            const bool cls = (free_l || l == v) && T.st[l].d0 != T.st[l].d1 &&
-                                             nd_by_rule(make_root(T.st[l].w, (int)T.st[l].p));
-                            const uint32_t mc = (uint32_t)ballot(cls);
-                            uint32_t mf = mc & ~(1u << v);
-                            if ((mc >> v) & 1u) {
-                                if (prof) {
-                                    tpr[3] += 1;
-                                    if (mf) tpr[4] += 1;
-                                }
-                                for (int att = 0; att < 2 && mf && v2 < 0 && k_pair; ++att) {
-                                    const int c2 = __ffs(mf) - 1;
-                                    mf &= mf - 1u;
-                                    int won2 = 0;
-                                    if (l == 0) {
-                                        const unsigned old = T.claim[c2];
-                                        won2 = old != qtag && atomicCAS(&T.claim[c2], old, qtag) == old;
-                                        if (won2) atomicAdd(&T.ncl, 1);
-                                    }
-                                    if (uniform(won2)) v2 = c2;
-                                }
-                            }
                         }
                         const unsigned long long q0 = prof ? wall_clock64() : 0ull;
                         // the pair in one pass (job_records_pair), else the item's
@@ -604,7 +646,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                                 tpr[6] += 1;
                             }
                         }
-                        const int nv = !PAIR ? 1 : (v < 0 ? 0 : (v2 >= 0 ? 2 : 1));
+                        const int nv = v < 0 ? 0 : (PAIR && v2 >= 0 ? 2 : 1);
                         for (int q = 0; q < nv; ++q) {
                             const int vq = q ? v2 : v;
                             const unsigned long long q1 = prof ? wall_clock64() : 0ull;
@@ -645,18 +687,10 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                         const int v = ld & (FL - 1), k = ld / FL;
                         const bool mine = k < 2 && act(v);
                         if (pipelined) {
-                            for (unsigned spin = 0;; ++spin) {
-                                const bool pend =
-                                    mine &&
-                                    __hip_atomic_load(&T.chosen[v], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != qtag;
-                                if (!ballot(pend)) break;
-                                if (spin >= (1u << 24)) {   // bounded
-                                    if (l == 0) atomicOr(f.e.err_flags, BGX_ERRF_WAIT_BOUND);
-                                    break;
-                                }
-                                __builtin_amdgcn_s_sleep(1);
-                            }
-                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                            // one word per poll: the stepped bits cover [lo, hi)
+                            const WaveClaimOps cops{l};
+                            if (!claim_wait_stepped(cops, T.cw, claim_range(lo, hi)) && l == 0)   // bounded
+                                atomicOr(f.e.err_flags, BGX_ERRF_WAIT_BOUND);
                         }
                         const unsigned long long d1 = prof ? wall_clock64() : 0ull;
                         if (mine)
@@ -677,10 +711,12 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
                     __syncthreads();
                 }
             }
-            if (prof) tw[0] += wall_clock64() - m0;
+            const unsigned long long m1 = prof ? wall_clock64() : 0ull;
+            if (prof) tw[0] += m1 - m0;
             tick(3);
             if (t == 0) T.go[(step + 1) & 1] = ticket(step + 1);   // as late as the step allows
             __syncthreads();   // step s's lanes are stepped and step s + 1's jobs are done
+            if (prof) twt[2] += wall_clock64() - m1;
             tick(4);
             if (prof && t == 0 && step >= 0) ph[5] += 1;
             if (prof && t == 0) {
@@ -825,6 +861,7 @@ __global__ __launch_bounds__(64 * FCfg<FL>::NW, FCfg<FL>::WPE) void fused_step_k
             atomicAdd(P + 23, tms[2]);
             for (int k = 0; k < 7; ++k) atomicAdd(P + 88 + k, tpr[k]);
             for (int k = 0; k < 3; ++k) atomicAdd(P + 95 + k, tdr[k]);
+            for (int k = 0; k < 3; ++k) atomicAdd(P + 98 + k, twt[k]);
         }
     }
     if (t == 0) {

@@ -55,6 +55,12 @@ void fused_prof_report(const unsigned long long* p, int n_slots, FILE* out, cons
     fprintf(out, "[bgx fused prof] tier-1 pair items: %.0f pairs formed (%.2f per workgroup step), %.2f us each, "
             "%.2f wave-us per workgroup step\n", s[94], s[94] / n, s[93] / (s[94] > 0 ? s[94] : 1) / 100,
             s[93] / n / 100);
+    // the waits of every wave (words 98..100, lane 0 of each wave): the choice
+    // items' wait for their tiles, the job items' claim (mask polls and
+    // fetch-ands, bgx_claim.h), the step's end barrier
+    fprintf(out, "[bgx fused prof] waits per wave-step: choice tile wait %.2f, job claim %.2f, end barrier %.2f us "
+            "(%.2f, %.2f, %.2f wave-us per workgroup step)\n", s[98] / nws / 100, s[99] / nws / 100,
+            s[100] / nws / 100, s[98] / n / 100, s[99] / n / 100, s[100] / n / 100);
     // the last launch, per workgroup: duration spread, dispatch skew, and the
     // rows / tier-2 jobs of the slowest vs the median workgroup
     std::vector<std::pair<double, int>> dur;
