@@ -192,6 +192,26 @@ int bgx_engine_destroy(bgx_engine* e);
 int bgx_set_weights(bgx_engine* e, const float* h_W1, const float* h_b1, const float* h_w2,
                     const float* h_b2, float temperature, uint64_t version);
 
+/* bgx_set_weights with the weights read from device memory on `stream`: the
+ * learner's hand-off (bgx/learner.py), which moves no weight and no fragment
+ * through the host. d_params [25601] fp32 in state_dict order: fc1.weight
+ * [128][198], fc1.bias [128], value_head.weight [128], value_head.bias [1] (a
+ * trainer's flat parameters). Two launches on `stream`, ordered behind the
+ * engine's last stream by an event when the two differ (no host wait for the
+ * engine's stream): a check that applies the weight limit above on the device
+ * and finds the scale exponent, and a pack that builds the MFMA fragments and
+ * the network's fp32 copies with the host path's arithmetic, bit for bit, and
+ * writes nothing when the check failed. The call then waits for `stream` once,
+ * for 16 bytes: the verdict, and the two scalars that travel in the step
+ * launches' arguments (value_head.bias, the feature scale). A failed check is
+ * BGX_E_ARG with bgx_set_weights' message (tensor, index, value) and leaves the
+ * previous network in force. An engine without a network gets one. A captured
+ * step graph is dropped when the temperature or one of the two scalars changes.
+ * The exponent is read from the bits of max|log2(e) w|, so it is exact where the
+ * host path's floor(log2()) can round up one ulp below a power of two. */
+int bgx_set_weights_device(bgx_engine* e, const float* d_params, float temperature, uint64_t version,
+                           void* stream);
+
 /* Match mode: two networks head to head (which of two checkpoints plays
  * better?). Network 0 is the one bgx_set_weights sets; network 1, the
  * opponent, is set here. In episode k (the lane's episode counter, the header's
@@ -373,7 +393,10 @@ enum {
     BGX_PEEK_CAND_ROWS = 5,   /* u32 [cand_cap][8] packed candidate boards */
     BGX_PEEK_VALUES = 6,      /* f32 [L + cand_cap] V of the lane rows, then of the candidates */
     BGX_PEEK_SEL = 7,         /* i32 [L][4] K = 4: the chosen candidate rows (-1: fewer than 4 moves) */
-    BGX_PEEK_JOB_VAL = 8      /* f32 [jobs] top-5 mean of the replies per (candidate, roll) */
+    BGX_PEEK_JOB_VAL = 8,     /* f32 [jobs] top-5 mean of the replies per (candidate, roll) */
+    BGX_PEEK_NET_FRAG = 9     /* network 0 as the step launches read it: its split-fp16 fragments
+                                 (6656 x 16 bytes), then the feature scale and value_head.bias as two
+                                 f32; fused and phased engines, once weights are set */
 };
 int bgx_engine_peek(bgx_engine* e, int buf, void* h_out, uint64_t bytes, uint64_t* needed);
 
@@ -540,6 +563,18 @@ int bgx_td_afterstate_update_batched(const uint32_t* d_records, const uint32_t* 
 /* bytes of device workspace bgx_td_afterstate_update_batched needs for n_records
  * records (bgx_tdlambda_batch_workspace plus one int32 per record); pure host arithmetic */
 int bgx_td_afterstate_batch_workspace(int n_records, uint64_t* bytes);
+
+/* The d_offs of the updates above from a harvest's headers, on the device:
+ * d_offs[0] = 0 and d_offs[k + 1] = d_offs[k] + d_headers[k][3] (n_records;
+ * header word 2 is a position in the lane's ring, not an offset into the
+ * harvest's records). d_headers [n_eps][16] u32 (a ticket's own array will do),
+ * d_offs [n_eps + 1]; n_eps = 0 writes d_offs[0] only. One launch of one
+ * workgroup on `stream`, on the calling thread's current device: asynchronous,
+ * no allocation, no host wait, so it can be captured into a graph. BGX_E_ARG
+ * for n_eps < 0, a null d_offs, a null d_headers with n_eps > 0 or a pointer
+ * that is not 4-byte aligned, before the device is touched. */
+int bgx_episode_offsets(const uint32_t* d_headers /* [n_eps][16] */, int n_eps, int32_t* d_offs /* [n_eps + 1] */,
+                        void* stream);
 
 /* Copy-engine transfer helpers (bgx/hostgather.py: the episode gather of
  * the ranks of one node through host shared memory, replacing the pickled

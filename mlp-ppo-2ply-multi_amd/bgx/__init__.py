@@ -9,6 +9,8 @@ Public surface:
   bgx.match    two networks head to head: play(a, b, games), tally(headers); python -m bgx.match
   bgx.rollout  play given positions out: rollout(weights, boards, player), summarize(counts);
                python -m bgx.rollout
+  bgx.learner  Learner: self-play and batched TD updates on one GPU with no host round trips;
+               python -m bgx.learn
 
 The re-exports below load on first use (PEP 562), so `import bgx.records`
 (the CPU-side queue's wire format) pulls in neither torch nor libbgx.so.
@@ -20,7 +22,7 @@ _EXPORTS = {
     "Engine": ".engine", "Harvest": ".engine",
     "BackgammonPolicyNetwork": ".net",
 }
-_SUBMODULES = ("ops", "dist", "episodes", "records", "trainer", "net", "engine", "match", "rollout")
+_SUBMODULES = ("ops", "dist", "episodes", "records", "trainer", "net", "engine", "match", "rollout", "learner", "learn")
 
 __all__ = list(_EXPORTS) + ["ops"]
 

@@ -72,6 +72,8 @@ SIGNATURES = {
     "bgx_engine_create": (c_int, [c_int, ctypes.POINTER(Config), ctypes.POINTER(c_void_p)]),
     "bgx_engine_destroy": (c_int, [c_void_p]),
     "bgx_set_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_u64]),
+    "bgx_set_weights_device": (c_int, [c_void_p, c_void_p, c_float, c_u64, c_void_p]),
+    "bgx_episode_offsets": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "bgx_engine_set_dice": (c_int, [c_void_p, c_void_p, c_int]),
     "bgx_engine_set_start": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_uint32]),
     "bgx_rollout_tally": (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.c_uint32, c_void_p, c_void_p]),

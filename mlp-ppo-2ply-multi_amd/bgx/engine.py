@@ -83,6 +83,23 @@ class Engine:
                                     int(version)), "bgx_set_weights")
         self.version, self.temperature = int(version), float(temperature)
 
+    def set_weights_device(self, params, temperature=1.5, version=1, stream=None):
+        """set_weights from a device tensor (bgx_set_weights_device): `params`
+        float32 [25601] in state_dict order (fc1.weight, fc1.bias,
+        value_head.weight, value_head.bias), e.g. a DeviceTrainer's flat
+        parameters. The fragments are built on the device, on `stream`, behind
+        the engine's queued steps; the call waits for `stream` once. Raises
+        BgxError for weights the scheme cannot hold (the previous network stays)."""
+        if not isinstance(params, torch.Tensor) or not params.is_cuda or params.dtype != torch.float32 \
+                or not params.is_contiguous() or params.numel() != 25601:
+            raise ValueError("params must be a contiguous float32 device tensor of 25601 elements")
+        if params.device != self.device:
+            raise ValueError(f"params are on {params.device}, the engine on {self.device}")
+        with torch.cuda.device(self.device):
+            check(lib().bgx_set_weights_device(self._h, params.data_ptr(), float(temperature), int(version),
+                                               stream_handle(stream)), "bgx_set_weights_device")
+        self.version, self.temperature = int(version), float(temperature)
+
     def set_opponent(self, weights):
         """Match mode (bgx_engine_set_opponent, bgx/match.py): `weights` become
         network 1, the opponent of the network set_weights sets; player p of
@@ -181,7 +198,9 @@ class Engine:
 
     PEEK = {"lane_rows": (0, "<u4", 8), "player": (1, "u1", 1), "dice": (2, "u1", 2), "cand_off": (3, "<i4", 1),
             "cand_cnt": (4, "<i4", 1), "cand_rows": (5, "<u4", 8), "values": (6, "<f4", 1), "sel": (7, "<i4", 4),
-            "job_val": (8, "<f4", 21)}
+            "job_val": (8, "<f4", 21),
+            # network 0 as the step launches read it: fragment bytes, then the feature scale and b2 (two f32)
+            "net_frag": (9, "u1", 1)}
 
     def peek(self, name):
         """Test hook (bgx_engine_peek): a host copy of one of the phased

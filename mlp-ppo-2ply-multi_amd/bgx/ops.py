@@ -246,6 +246,27 @@ def rollout_tally(headers, start_player, n_pos, max_episode, counts, stream=None
     return counts
 
 
+def episode_offsets(headers, out=None, stream=None):
+    """offs int32 [n + 1] of a harvest's headers (int32 [n, 16] on the device),
+    computed there (bgx_episode_offsets): offs[0] = 0, offs[k + 1] = offs[k] +
+    headers[k, 3]. Asynchronous on the stream; nothing is read on the host. `out`:
+    a device int32 tensor of at least n + 1 elements to write into (no allocation
+    then); the result is its first n + 1 elements."""
+    require_cuda(headers)
+    if headers.dtype != torch.int32 or headers.dim() != 2 or headers.shape[1] != 16:
+        raise ValueError("headers must be int32 [n, 16]")
+    n = int(headers.shape[0])
+    if out is None:
+        out = torch.empty((n + 1,), dtype=torch.int32, device=headers.device)
+    else:
+        require_cuda(out)
+        if out.dtype != torch.int32 or out.dim() != 1 or out.numel() < n + 1 or out.device != headers.device:
+            raise ValueError("out must be int32 [>= n + 1] on the headers' device")
+    with torch.cuda.device(headers.device):
+        check(lib().bgx_episode_offsets(ptr(headers), n, ptr(out), stream_handle(stream)), "bgx_episode_offsets")
+    return out[:n + 1]
+
+
 def load_pth(path):
     """A reference checkpoint (torch.save of BackgammonPolicyNetwork.state_dict(),
     parameter_manager.py:115-151: fc1.weight / fc1.bias / value_head.weight /

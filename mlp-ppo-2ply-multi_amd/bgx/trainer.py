@@ -57,6 +57,14 @@ the mover's, the mover taken from the observation's feature 197);
 batched=True with backend="hip" runs bgx_td_afterstate_update_batched at every
 lam / zero_sum. The sequential HIP kernel stays the reference's TD(0) on
 before-move positions.
+
+update_device(headers, records) is update_records for a loop that never leaves
+the device (bgx/learner.py): batched=True with backend="hip" only, device
+tensors in (a harvest ticket's own arrays will do), the episode offsets from
+bgx_episode_offsets, no tensor read on the host, the metrics summed in a device
+tensor. metrics(), sync_module(), state_dict() and publish() bring the host's
+views up to date when asked; `params` is the flat tensor
+Engine.set_weights_device takes.
 """
 from __future__ import annotations
 
@@ -108,6 +116,8 @@ class DeviceTrainer:
         self.total_episodes = 0
         self._flat = None   # HIP backend state: params / Adam m / v (flat, state_dict order), step
         self._work = None   # batched HIP backend: the workspace tensor, regrown on demand
+        self._dev = None    # update_device: the metrics accumulator, the offsets buffer and the host-side counts
+        self._gamma_host = float(self.gamma)   # read once: update_device reads no device tensor
 
     @staticmethod
     def batch_shape():
@@ -340,6 +350,138 @@ class DeviceTrainer:
                                                    ptr(metrics), None, ptr(self._work), self._work.numel(), stream),
                       "bgx_td0_update_batched")
         return self._finish_hip(metrics, hdr, lens)
+
+    # ------------------------------------------------------------ device-resident update
+    def update_device(self, headers, records):
+        """update_records for a learner that keeps everything on the device
+        (bgx/learner.py): `headers` int32 [n, 16] and `records` int32 [m, 12] are
+        contiguous device tensors, e.g. a harvest ticket's own arrays
+        (Engine.harvest_fetch(clone=False)). Needs batched=True and
+        backend="hip". No tensor is read on the host: the offsets come from
+        ops.episode_offsets, n and m from the shapes, the ABI call is the one
+        _update_hip_batched chooses (the headers go in as d_headers), and the
+        five metrics add up in a device tensor the trainer owns. The torch
+        module, the optimizer and the parameter manager are not touched:
+        metrics(), sync_module(), state_dict() and publish() bring the host up
+        to date when asked. On the same inputs and state the flat parameters,
+        moments and step count come out bit-identical to update_records'.
+
+        What update_records checks on the host (every episode has records, the
+        headers count exactly m records) cannot be checked here without a
+        round trip: the headers are trusted as the engine wrote them, and the
+        kernels clamp the offsets to [0, m] (no read past `records`).
+        Returns None; asynchronous on the trainer's current stream."""
+        import ctypes
+        from ._lib import check, lib, ptr, stream_handle
+        if not (self.batched and self.backend == "hip"):
+            raise ValueError("update_device needs batched=True and backend='hip' (the batched HIP update is the only "
+                             "one that runs without the host)")
+        for name, t, width in (("headers", headers, 16), ("records", records, 12)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int32 or t.dim() != 2 \
+                    or t.shape[1] != width or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous int32 device tensor [n, {width}]")
+            if t.device != self.device and not (self.device.index is None and t.device.type == "cuda"):
+                raise ValueError(f"{name} are on {t.device}, the trainer on {self.device}")
+        n_eps, n_rec = int(headers.shape[0]), int(records.shape[0])
+        if n_eps < 1:
+            raise ValueError("update_device: no episodes")
+        if n_rec < n_eps or n_rec >= 2 ** 31:
+            raise ValueError(f"update_device: {n_eps} episodes cannot hold {n_rec} records")
+        f = self._hip_state()
+        dev = f["p"].device
+        if self._dev is None or self._dev["metrics"].device != dev:
+            self._dev = {"metrics": torch.zeros(5, dtype=torch.float64, device=dev), "offs": None,
+                         "updates": 0, "episodes": 0, "records": 0}
+        d = self._dev
+        need = ctypes.c_uint64(0)
+        if self.afterstates:
+            check(lib().bgx_td_afterstate_batch_workspace(n_rec, ctypes.byref(need)),
+                  "bgx_td_afterstate_batch_workspace")
+        elif self.lam != 0.0 or self.zero_sum:
+            check(lib().bgx_tdlambda_batch_workspace(n_rec, ctypes.byref(need)), "bgx_tdlambda_batch_workspace")
+        else:
+            check(lib().bgx_td0_batch_workspace(n_rec, ctypes.byref(need)), "bgx_td0_batch_workspace")
+        # both buffers grow in steps, so a steady state allocates nothing
+        if self._work is None or self._work.numel() < need.value or self._work.device != dev:
+            self._work = torch.empty(need.value + need.value // 4, dtype=torch.uint8, device=dev)
+        if d["offs"] is None or d["offs"].numel() < n_eps + 1:
+            d["offs"] = torch.empty(2 * (n_eps + 1), dtype=torch.int32, device=dev)
+        clip = float(self.grad_clip) if self.grad_clip is not None else 0.0
+        lr = float(self.optimizer.param_groups[0]["lr"])
+        gamma = self._gamma_host
+        metrics = d["metrics"]
+        with torch.cuda.device(dev):   # the trainer's device and its current stream
+            s = torch.cuda.current_stream(dev)
+            stream = stream_handle(s)
+            offs = ops.episode_offsets(headers, out=d["offs"], stream=s)
+            if self.afterstates:
+                check(lib().bgx_td_afterstate_update_batched(ptr(records), ptr(headers), ptr(offs), n_eps, n_rec,
+                                                             ptr(f["p"]), ptr(f["m"]), ptr(f["v"]), ptr(f["step"]), lr,
+                                                             gamma, self.lam, TDF_ZERO_SUM if self.zero_sum else 0,
+                                                             clip, ptr(metrics), None, None, ptr(self._work),
+                                                             self._work.numel(), stream),
+                      "bgx_td_afterstate_update_batched")
+            elif self.zero_sum:
+                check(lib().bgx_td_update_batched(ptr(records), ptr(offs), n_eps, n_rec, ptr(f["p"]), ptr(f["m"]),
+                                                  ptr(f["v"]), ptr(f["step"]), lr, gamma, self.lam, TDF_ZERO_SUM, clip,
+                                                  ptr(metrics), None, None, ptr(self._work), self._work.numel(),
+                                                  stream),
+                      "bgx_td_update_batched")
+            elif self.lam != 0.0:
+                check(lib().bgx_tdlambda_update_batched(ptr(records), ptr(offs), n_eps, n_rec, ptr(f["p"]), ptr(f["m"]),
+                                                        ptr(f["v"]), ptr(f["step"]), lr, gamma, self.lam, clip,
+                                                        ptr(metrics), None, None, ptr(self._work), self._work.numel(),
+                                                        stream),
+                      "bgx_tdlambda_update_batched")
+            else:
+                check(lib().bgx_td0_update_batched(ptr(records), ptr(offs), n_eps, n_rec, ptr(f["p"]), ptr(f["m"]),
+                                                   ptr(f["v"]), ptr(f["step"]), lr, gamma, clip, ptr(metrics), None,
+                                                   ptr(self._work), self._work.numel(), stream),
+                      "bgx_td0_update_batched")
+        d["updates"] += 1
+        d["episodes"] += n_eps
+        d["records"] += n_rec
+        self.total_episodes += n_eps
+
+    @property
+    def params(self):
+        """The flat float32 [25601] device parameters (state_dict order) the HIP
+        updates write in place: what Engine.set_weights_device takes."""
+        return self._hip_state()["p"]
+
+    def metrics(self, reset=True):
+        """update_records' metrics dict over the update_device calls since the
+        last reset, each value a mean per episode (one host read of the device
+        accumulator); None when there were none. No win_counts: those would
+        need the headers on the host."""
+        d = self._dev
+        if d is None or d["updates"] == 0:
+            return None
+        a = d["metrics"].tolist()
+        n = max(1, d["episodes"])
+        out = {"loss": a[0] / n, "grad_norm": a[1] / n, "td_error": a[2] / n, "predicted_value": a[3] / n,
+               "reward": a[4] / n, "episode_length": float(d["records"]) / n, "episodes": d["episodes"],
+               "updates": d["updates"]}
+        if reset:
+            d["metrics"].zero_()
+            d["updates"] = d["episodes"] = d["records"] = 0
+        return out
+
+    def sync_module(self):
+        """The torch module and optimizer follow the HIP backend's flat state
+        (update_device leaves them behind)."""
+        if self._flat is not None:
+            self._sync_module()
+
+    def state_dict(self):
+        """The current weights as the module's state_dict, after sync_module()."""
+        self.sync_module()
+        return self.policy_network.state_dict()
+
+    def publish(self):
+        """The current weights to the parameter manager (what every
+        update_records call does; update_device leaves it to the caller)."""
+        self.parameter_manager.set_parameters(self.state_dict())
 
     def _finish_hip(self, metrics, hdr, lens):
         """After a HIP update: the module / optimizer follow the flat state, the

@@ -16,6 +16,7 @@
 #include "bgx_domain.h"
 #include "bgx_frag.h"
 #include "bgx_host.h"
+#include "bgx_pack.h"
 
 static thread_local std::string g_err;
 
@@ -475,6 +476,19 @@ int bgx_td_afterstate_update_batched(const uint32_t* d_records, const uint32_t* 
     return update_batched("bgx_td_afterstate_update_batched", true, true, d_records, d_headers, d_offs, n_eps,
                           n_records, d_params, d_adam_m, d_adam_v, d_step, lr, gamma, lambda, flags, grad_clip,
                           d_metrics, d_grad_out, d_target_out, d_work, work_bytes, stream);
+}
+
+int bgx_episode_offsets(const uint32_t* d_headers, int n_eps, int32_t* d_offs, void* stream) {
+    return guarded("bgx_episode_offsets", [&]() -> int {
+        if (n_eps < 0 || !d_offs || (n_eps > 0 && !d_headers))
+            return fail(BGX_E_ARG, "bgx_episode_offsets: bad arguments (n_eps=%d)", n_eps);
+        if ((uintptr_t)d_headers % 4 != 0 || (uintptr_t)d_offs % 4 != 0)
+            return fail(BGX_E_ARG, "bgx_episode_offsets: d_headers / d_offs is not 4-byte aligned");
+        // one launch on the caller's current device: no allocation, no pointer
+        // query and no wait, so the call can be captured into a graph
+        HIP_TRY(bgx_launch_episode_offsets(d_headers, n_eps, d_offs, (hipStream_t)stream));
+        return BGX_OK;
+    });
 }
 
 int bgx_reply_moves(const uint8_t* d_boards, const uint8_t* d_opponent, int n, uint32_t* d_out, int cap,

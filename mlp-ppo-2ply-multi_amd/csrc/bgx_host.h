@@ -264,6 +264,11 @@ struct bgx_engine {
     bool prof_enabled = false;
     int fused_fl = 0;              // BGX_FUSED_LANES: fused 1-ply lanes per workgroup (16 / 32; 0 = auto)
     int fused_pair = 1;            // BGX_FUSED_PAIR: two rule-mode non-doubles jobs per wave (0 = off; A/B, tests)
+    // bgx_set_weights_device: the check launch's verdict (bgx::PackInfo, 16 B), its
+    // pinned host copy, and the event that orders the hand-off behind `last`
+    DevBuf<uint32_t> wd_info;
+    HostWords wd_hinfo;
+    Event wd_ev;
     DevBuf<uint8_t> dice_tab;      // bgx_engine_set_dice
     DevBuf<uint32_t> start_tab;    // bgx_engine_set_start (EngineDev::start_tab)
     // optional hipGraph of the last n_steps sequence

@@ -1,10 +1,12 @@
 // bgx_host_engine.cpp — engine lifetime and modes: create / destroy, weights,
 // scripted dice, match mode, rollout mode, and the host's views of the
 // engine's state (stats, peek, timing).
+#include <cmath>
 #include <cstring>
 
 #include "bgx_domain.h"
 #include "bgx_host.h"
+#include "bgx_pack.h"
 
 // every lane restarts from BackgammonEnv.reset, or in rollout mode from its
 // start-table position: new scripted dice, and entering or leaving match mode
@@ -250,6 +252,70 @@ int bgx_set_weights(bgx_engine* e, const float* h_W1, const float* h_b1, const f
     });
 }
 
+int bgx_set_weights_device(bgx_engine* e, const float* d_params, float temperature, uint64_t version, void* stream) {
+    return guarded("bgx_set_weights_device", [&]() -> int {
+        (void)version;
+        // (the argument checks read nothing of *e)
+        if (!e) return fail(BGX_E_ARG, "bgx_set_weights_device: null engine");
+        if (!d_params) return fail(BGX_E_ARG, "bgx_set_weights_device: null d_params");
+        if ((uintptr_t)d_params % 4 != 0) return fail(BGX_E_ARG, "bgx_set_weights_device: d_params is not 4-byte aligned");
+        if (!(temperature > 0.0f)) return fail(BGX_E_ARG, "temperature=%g", (double)temperature);
+        HIP_TRY(hipSetDevice(e->device));
+        hipStream_t s = (hipStream_t)stream;
+        if (!e->wd_info || !e->wd_hinfo || !e->wd_ev) {
+            if (int rc = e->wd_info.alloc(4)) return rc;
+            if (hipHostMalloc((void**)e->wd_hinfo.put(), sizeof(bgx::PackInfo), hipHostMallocDefault) != hipSuccess ||
+                hipEventCreateWithFlags(e->wd_ev.put(), hipEventDisableTiming) != hipSuccess)
+                return fail(BGX_E_HIP, "bgx_set_weights_device: pinned buffer / event creation failed");
+        }
+        // an engine without a network gets one; it is kept only when the weights pass
+        std::unique_ptr<bgx_net> fresh;
+        bgx_net* n = e->net.get();
+        if (!n) {
+            fresh.reset(new bgx_net());
+            n = fresh.get();
+            if (n->W1.alloc(128 * 198) || n->b1.alloc(128) || n->w2.alloc(128) || n->wfrag.alloc(bgx::PK_NFRAG) ||
+                n->rowc.alloc(128 * 4))
+                return BGX_E_HIP;
+        }
+        // the engine's queued steps read the arrays the pack launch rewrites: on
+        // another stream the hand-off goes behind them by an event, no host wait
+        if (e->last != s) {
+            HIP_TRY(hipEventRecord(e->wd_ev, e->last));
+            HIP_TRY(hipStreamWaitEvent(s, e->wd_ev, 0));
+        }
+        bgx::PackInfo* d_info = (bgx::PackInfo*)e->wd_info.get();
+        HIP_TRY(bgx_launch_weights_check(d_params, d_info, s));
+        HIP_TRY(bgx_launch_weights_pack(d_params, d_info, n->wfrag, n->W1, n->b1, n->w2, n->rowc, s));
+        HIP_TRY(hipMemcpyAsync(e->wd_hinfo, d_info, sizeof(bgx::PackInfo), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));   // the call's one host wait: b2 and 2^-e are launch arguments (set_net)
+        bgx::PackInfo pi;
+        std::memcpy(&pi, e->wd_hinfo, sizeof(pi));
+        if (pi.rule != bgx::PK_RULE_OK) {   // net_upload's messages; the pack launch wrote nothing
+            const int at = pi.index;
+            const char* name = at < bgx::PK_B1 ? "W1" : at < bgx::PK_W2 ? "b1" : at < bgx::PK_B2 ? "w2" : "b2";
+            const int idx = at < bgx::PK_B1 ? at : at < bgx::PK_W2 ? at - bgx::PK_B1 : at < bgx::PK_B2 ? at - bgx::PK_W2 : 0;
+            if (pi.rule == bgx::PK_RULE_NONFINITE) return fail(BGX_E_ARG, "weights: %s[%d] is not finite", name, idx);
+            float v = 0.0f;
+            HIP_TRY(hipMemcpy(&v, d_params + at, 4, hipMemcpyDeviceToHost));
+            return fail(BGX_E_ARG, "weights: %s[%d] = %g: max|log2(e) w| must stay below 2^26 (split-fp16 scaling limit)",
+                        name, idx, (double)v);
+        }
+        float b2 = 0.0f;
+        std::memcpy(&b2, &pi.b2_bits, 4);
+        const float feat_scale = (float)std::ldexp(1.0, -pi.e);
+        // a captured graph holds the temperature, and with it b2 and 2^-e, by
+        // value (enqueue_steps' set_net): dropped when any of the three changes
+        if (e->d.temperature != temperature || n->b2 != b2 || n->feat_scale != feat_scale)
+            if (int rc = drop_graph(e)) return rc;
+        n->feat_scale = feat_scale;
+        n->b2 = b2;
+        if (fresh) e->net = std::move(fresh);
+        e->d.temperature = temperature;
+        return BGX_OK;
+    });
+}
+
 int bgx_engine_set_opponent(bgx_engine* e, const float* h_W1, const float* h_b1, const float* h_w2,
                             const float* h_b2) {
     return guarded("bgx_engine_set_opponent", [&]() -> int {
@@ -397,6 +463,19 @@ int bgx_engine_peek(bgx_engine* e, int buf, void* h_out, uint64_t bytes, uint64_
         const size_t L = (size_t)e->cfg.lanes;
         const void* src = nullptr;
         size_t n = 0;
+        if (buf == BGX_PEEK_NET_FRAG) {   // network 0 as the launches read it; fused and phased engines alike
+            if (!e->net) return fail(BGX_E_STATE, "bgx_engine_peek: the engine has no network yet");
+            const size_t nf = (size_t)bgx::PK_NFRAG * 16;
+            if (needed) *needed = nf + 8;
+            if (!h_out) return BGX_OK;
+            if (bytes < nf + 8) return fail(BGX_E_ARG, "bgx_engine_peek: %llu bytes < %zu", (unsigned long long)bytes, nf + 8);
+            HIP_TRY(hipSetDevice(e->device));
+            if (e->last) HIP_TRY(hipStreamSynchronize(e->last));
+            HIP_TRY(hipMemcpy(h_out, e->net->wfrag, nf, hipMemcpyDeviceToHost));
+            const float tail[2] = {e->net->feat_scale, e->net->b2};
+            std::memcpy((char*)h_out + nf, tail, 8);
+            return BGX_OK;
+        }
         switch (buf) {
         case BGX_PEEK_LANE_ROWS: src = e->rows; n = L * 8 * 4; break;
         case BGX_PEEK_PLAYER: src = e->d.player; n = L; break;
