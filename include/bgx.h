@@ -576,6 +576,44 @@ int bgx_td_afterstate_batch_workspace(int n_records, uint64_t* bytes);
 int bgx_episode_offsets(const uint32_t* d_headers /* [n_eps][16] */, int n_eps, int32_t* d_offs /* [n_eps + 1] */,
                         void* stream);
 
+/* A harvest in canonical order, on the device. A harvest's episodes come in the
+ * device's completion order, which differs from run to run; the batched updates
+ * sum in the order they are given, so their bits depend on it. This call
+ * re-lays a harvest (bgx_harvest's d_headers [n_eps][16] and d_records
+ * [n_records][12]) by the key (header word 0, the global lane; word 1, the
+ * episode number), ascending, both compared as unsigned:
+ *   d_out_headers [n_eps][16]    the input headers, each verbatim, in key order
+ *   d_out_records [n_records][12] each episode's records, contiguous and
+ *                                verbatim, in the order of d_out_headers
+ *   d_out_offs [n_eps + 1]       the exclusive prefix sum of word 3 over
+ *                                d_out_headers (bgx_episode_offsets of them)
+ * The outputs are a function of the set of input episodes: any arrival order of
+ * the same episodes gives the same bytes. Word 0 must lie in [lane_base,
+ * lane_base + lanes) (an engine's bgx_config.lane_base and lanes). Two launches
+ * (csrc/bgx_canon.h: an index launch of one workgroup, a copy launch of a wave
+ * per episode; integer atomics only). *d_status, a u32 the call never clears,
+ * gets the BGX_CANON_* bits of what the headers break; with a bit set the
+ * outputs are unspecified, but nothing outside them and d_work is written and
+ * nothing outside the inputs is read (every index is clamped on the device).
+ * d_work: at least bgx_harvest_canonical_workspace(n_eps, lanes) bytes, free
+ * for reuse once the call's stream work is done. n_eps = 0 writes
+ * d_out_offs[0] = 0 only. Runs on the calling thread's current device and on
+ * `stream`: asynchronous, no allocation, no host wait (capturable).
+ * BGX_E_ARG, before the device is touched: a negative n_eps, n_records or
+ * lane_base, lanes < 1, a null d_out_offs or d_status, a null array that the
+ * sizes need, d_out_offs or d_status not 4-byte aligned, any other pointer not
+ * 16-byte aligned, work_bytes too small, an output (d_work included) that
+ * overlaps an input or another output. */
+#define BGX_CANON_LANE_RANGE 1u   /* a word 0 outside [lane_base, lane_base + lanes) */
+#define BGX_CANON_DUPLICATE 2u    /* two headers share a key */
+#define BGX_CANON_RECORDS 4u      /* word 3 does not sum to n_records */
+int bgx_harvest_canonical(const uint32_t* d_headers, const uint32_t* d_records, int n_eps, int n_records,
+                          int lane_base, int lanes,
+                          uint32_t* d_out_headers, uint32_t* d_out_records, int32_t* d_out_offs,
+                          uint32_t* d_status, void* d_work, uint64_t work_bytes, void* stream);
+/* bytes of device workspace bgx_harvest_canonical needs; pure host arithmetic */
+int bgx_harvest_canonical_workspace(int n_eps, int lanes, uint64_t* bytes);
+
 /* Copy-engine transfer helpers (bgx/hostgather.py: the episode gather of
  * the ranks of one node through host shared memory, replacing the pickled
  * queue of src/main.py:115-133 / multi/experience_queue.py:5-13 without

@@ -74,6 +74,9 @@ SIGNATURES = {
     "bgx_set_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_u64]),
     "bgx_set_weights_device": (c_int, [c_void_p, c_void_p, c_float, c_u64, c_void_p]),
     "bgx_episode_offsets": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "bgx_harvest_canonical": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_u64, c_void_p]),
+    "bgx_harvest_canonical_workspace": (c_int, [c_int, c_int, ctypes.POINTER(c_u64)]),
     "bgx_engine_set_dice": (c_int, [c_void_p, c_void_p, c_int]),
     "bgx_engine_set_start": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_uint32]),
     "bgx_rollout_tally": (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.c_uint32, c_void_p, c_void_p]),

@@ -27,8 +27,18 @@ it, as the harvest contract requires.
 
 Episode order within a harvest is the device's completion order (the fused
 engine's workgroups append as they finish), and the update sums in that order:
-two runs of one seed play the same games in chunk 0 but do not repeat bit for
-bit afterwards.
+by default two runs of one seed play the same games in chunk 0 but do not repeat
+bit for bit afterwards. deterministic=True removes that: before the update,
+ticket c - 1 is put into the canonical order of ops.canonical_harvest (by lane,
+then by episode number) on the learner's stream, into buffers the learner owns,
+and the trainer reads those. The set of episodes in a ticket is fixed by the
+seed, so a run is then a pure function of the learner's arguments: digest()
+repeats to the bit from run to run, and on_update's headers / records are the
+canonical arrays (the ticket's own are raw_headers / raw_records), valid until
+the next update. The canonical launches OR what they find wrong with the headers
+into a status word on the device; sync() reads it and raises BgxError when it is
+not zero, so no update waits for it. balance=True hands out lane-steps by
+ticket, so its games depend on timing: it cannot be combined.
 
 A hand-off the scheme cannot hold (non-finite weights, |w| past the split-fp16
 limit) raises BgxError; the engine keeps its previous network and can go on
@@ -37,9 +47,12 @@ stepping.
 from __future__ import annotations
 
 import collections
+import hashlib
 
 import torch
 
+from . import ops
+from ._lib import BgxError
 from .engine import Engine
 from .net import BackgammonPolicyNetwork
 from .trainer import GAMMA, GRAD_CLIP_THRESHOLD, LEARNING_RATE, DeviceTrainer
@@ -81,7 +94,11 @@ def _state_dict_from(weights, seed):
 class Learner:
     def __init__(self, lanes, steps_per_chunk, seed=0, weights=None, lam=0.0, zero_sum=False, afterstates=False,
                  lr=LEARNING_RATE, gamma=GAMMA, grad_clip=GRAD_CLIP_THRESHOLD, temperature=reference_temperature,
-                 balance=False, on_update=None, device=None):
+                 balance=False, on_update=None, device=None, deterministic=False):
+        if deterministic and balance:
+            raise ValueError("deterministic=True needs balance=False: the balanced launch hands out lane-steps by "
+                             "ticket, so the games themselves depend on timing")
+        self.deterministic = bool(deterministic)
         self.engine = Engine(lanes=lanes, seed=seed, ply=1, fused=True, balance=balance, device=device)
         if not 1 <= int(steps_per_chunk) <= self.engine.max_steps_per_call:
             raise ValueError(f"steps_per_chunk must be in 1 .. {self.engine.max_steps_per_call}")
@@ -101,7 +118,8 @@ class Learner:
         self.records = 0
         self.log = []         # (ticket, episodes, updated) of every ticket looked at
         self._timed = collections.deque()   # (kind, start event, end event), resolved once complete
-        self.gpu_ms = {"step": 0.0, "update": 0.0}
+        self.gpu_ms = {"step": 0.0, "update": 0.0, "canon": 0.0}
+        self._canon = None    # deterministic: the canonical arrays, the workspace and the status word
         # the first network goes the host's way (there is nothing to overlap yet)
         self.engine.set_weights(self.params.get_parameters(), float(temperature(self.version)), self.version)
 
@@ -117,6 +135,23 @@ class Learner:
             if wait:
                 b.synchronize()
             self.gpu_ms[kind] += a.elapsed_time(b)
+
+    def _canonical(self, h):
+        """Ticket h in canonical order, in the learner's own buffers (the current
+        stream is the learner's). They grow in steps: a steady state allocates nothing."""
+        n, m = h.n_episodes, h.n_records
+        c = self._canon
+        if c is None:
+            c = self._canon = {"headers": None, "records": None, "offs": None, "work": None,
+                               "status": torch.zeros(1, dtype=torch.int32, device=self.device)}
+        need = ops.canonical_workspace(n, self.lanes)
+        for key, rows, shape, dtype in (("headers", n, (16,), torch.int32), ("records", m, (12,), torch.int32),
+                                        ("offs", n + 1, (), torch.int32), ("work", need, (), torch.uint8)):
+            if c[key] is None or c[key].shape[0] < rows:
+                c[key] = torch.empty((rows + rows // 4 + 16,) + shape, dtype=dtype, device=self.device)
+        return ops.canonical_harvest(h.headers, h.records, lane_base=int(self.engine.cfg.lane_base), lanes=self.lanes,
+                                     out=(c["headers"], c["records"], c["offs"]), status=c["status"],
+                                     stream=self.stream, work=c["work"])
 
     def run_chunk(self):
         """One chunk of the schedule above; returns True when it made an update."""
@@ -138,7 +173,16 @@ class Learner:
         temp = float(self.temperature(version))
         with torch.cuda.stream(s):   # the trainer launches on its current stream
             a = self._mark()
-            self.trainer.update_device(h.headers, h.records)
+            headers, records, info = h.headers, h.records, {}
+            if self.deterministic:
+                headers, records, offs = self._canonical(h)
+                b = self._mark()
+                self._timed.append(("canon", a, b))
+                a = b
+                self.trainer.update_device(headers, records, offs=offs)
+                info = {"raw_headers": h.headers, "raw_records": h.records}
+            else:
+                self.trainer.update_device(headers, records)
             eng.set_weights_device(self.trainer.params, temp, version, stream=s)   # raises when rejected
             self._timed.append(("update", a, self._mark()))
             self.version = version
@@ -147,7 +191,7 @@ class Learner:
             self.records += h.n_records
             if self.on_update is not None:
                 self.on_update({"update": self.updates, "version": version, "temperature": temp, "chunk": c,
-                                "ticket": ticket - 1, "headers": h.headers, "records": h.records})
+                                "ticket": ticket - 1, "headers": headers, "records": records, **info})
         self._resolve()
         return True
 
@@ -169,6 +213,22 @@ class Learner:
         self.stream.synchronize()
         self.engine.sync()
         self._resolve(wait=True)
+        if self._canon is not None:
+            bits = int(self._canon["status"].item()) & 0xFFFFFFFF
+            if bits:
+                what = "; ".join(v for k, v in ops.CANON_BITS.items() if bits & k)
+                raise BgxError(f"canonical harvest order: status 0x{bits:x} ({what}): the updates since the last sync() "
+                               f"read unspecified arrays")
+
+    def digest(self):
+        """SHA-256 (hex) of the trainer's flat parameters, Adam moments and step
+        count as they stand once the stream's work is done; read on the host."""
+        self.stream.synchronize()
+        f = self.trainer._hip_state()
+        h = hashlib.sha256()
+        for key in ("p", "m", "v", "step"):
+            h.update(f[key].cpu().numpy().tobytes())
+        return h.hexdigest()
 
     def weights(self):
         """The trainer's current weights as host fp32 W1, b1, w2, b2."""

@@ -267,6 +267,83 @@ def episode_offsets(headers, out=None, stream=None):
     return out[:n + 1]
 
 
+CANON_BITS = {1: "a lane outside [lane_base, lane_base + lanes)", 2: "two episodes share (lane, episode number)",
+              4: "the headers' record counts do not sum to the records given"}
+
+
+def canonical_workspace(n_eps, lanes):
+    """Bytes of workspace canonical_harvest needs (bgx_harvest_canonical_workspace; host arithmetic)."""
+    need = ctypes.c_uint64(0)
+    check(lib().bgx_harvest_canonical_workspace(int(n_eps), int(lanes), ctypes.byref(need)),
+          "bgx_harvest_canonical_workspace")
+    return int(need.value)
+
+
+def canonical_harvest(headers, records, lane_base=0, lanes=None, out=None, status=None, stream=None, work=None):
+    """A harvest in canonical order, computed on the device (bgx_harvest_canonical):
+    the episodes of `headers` int32 [n, 16] / `records` int32 [m, 12] (contiguous
+    device tensors, e.g. a ticket's own arrays) ordered by (lane, episode number),
+    header words 0 and 1 as unsigned. Returns (headers [n, 16], records [m, 12],
+    offs int32 [n + 1]): the headers and each episode's records verbatim in that
+    order and episode_offsets of the new headers. Any arrival order of the same
+    episodes gives the same bytes. Asynchronous on the stream.
+
+    lane_base, lanes: the range of header word 0 (an Engine's lane_base and
+    lanes). lanes=None reads the largest lane from the headers on the host, which
+    waits for them; pass it to keep the call asynchronous.
+    out: three device tensors to write into, int32 [>= n, 16], [>= m, 12] and
+    [>= n + 1]; the results are views of their first rows. status: an int32 [1]
+    device tensor the call ORs CANON_BITS into and never clears (zero after a
+    harvest as the engine writes it; with a bit set the outputs are unspecified).
+    work: a uint8 device tensor of at least bgx_harvest_canonical_workspace
+    bytes. What is not given is allocated on the stream."""
+    for name, t, width in (("headers", headers, 16), ("records", records, 12)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int32 or t.dim() != 2 \
+                or t.shape[1] != width or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int32 device tensor [n, {width}]")
+    dev = headers.device
+    if records.device != dev:
+        raise ValueError(f"headers are on {dev}, records on {records.device}")
+    n, m = int(headers.shape[0]), int(records.shape[0])
+    if m >= 2 ** 31:
+        raise ValueError(f"canonical_harvest: {m} records")
+    lane_base = int(lane_base)
+    if lanes is None:
+        lanes = max(1, int(headers[:, 0].max()) - lane_base + 1) if n else 1
+    lanes = int(lanes)
+    if lane_base < 0 or lanes < 1:
+        raise ValueError(f"canonical_harvest: lane_base={lane_base} lanes={lanes}")
+    need = canonical_workspace(n, lanes)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(s):
+        if out is None:
+            out = (torch.empty((n, 16), dtype=torch.int32, device=dev), torch.empty((m, 12), dtype=torch.int32, device=dev),
+                   torch.empty((n + 1,), dtype=torch.int32, device=dev))
+        else:
+            shapes = ((n, 16, "[>= n, 16]"), (m, 12, "[>= m, 12]"), (n + 1, None, "[>= n + 1]"))
+            if len(out) != 3:
+                raise ValueError("out must be (headers, records, offs)")
+            for t, (rows, width, what) in zip(out, shapes):
+                if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int32 or t.device != dev \
+                        or not t.is_contiguous() or t.dim() != (1 if width is None else 2) or t.shape[0] < rows \
+                        or (width is not None and t.shape[1] != width):
+                    raise ValueError(f"out must be contiguous int32 tensors {what} on the headers' device")
+        if status is None:
+            status = torch.zeros(1, dtype=torch.int32, device=dev)
+        elif not isinstance(status, torch.Tensor) or status.dtype != torch.int32 or status.numel() != 1 \
+                or status.device != dev:
+            raise ValueError("status must be an int32 [1] tensor on the headers' device")
+        if work is None:
+            work = torch.empty(max(16, need), dtype=torch.uint8, device=dev)
+        elif not isinstance(work, torch.Tensor) or work.dtype != torch.uint8 or work.device != dev \
+                or not work.is_contiguous() or work.numel() < need:
+            raise ValueError(f"work must be a contiguous uint8 tensor of at least {need} bytes on the headers' device")
+        check(lib().bgx_harvest_canonical(ptr(headers), ptr(records), n, m, lane_base, lanes, ptr(out[0]), ptr(out[1]),
+                                          ptr(out[2]), ptr(status), ptr(work), work.numel(), stream_handle(s)),
+              "bgx_harvest_canonical")
+    return out[0][:n], out[1][:m], out[2][:n + 1]
+
+
 def load_pth(path):
     """A reference checkpoint (torch.save of BackgammonPolicyNetwork.state_dict(),
     parameter_manager.py:115-151: fc1.weight / fc1.bias / value_head.weight /

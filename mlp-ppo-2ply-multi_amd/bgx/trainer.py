@@ -352,7 +352,7 @@ class DeviceTrainer:
         return self._finish_hip(metrics, hdr, lens)
 
     # ------------------------------------------------------------ device-resident update
-    def update_device(self, headers, records):
+    def update_device(self, headers, records, offs=None):
         """update_records for a learner that keeps everything on the device
         (bgx/learner.py): `headers` int32 [n, 16] and `records` int32 [m, 12] are
         contiguous device tensors, e.g. a harvest ticket's own arrays
@@ -370,6 +370,9 @@ class DeviceTrainer:
         headers count exactly m records) cannot be checked here without a
         round trip: the headers are trusted as the engine wrote them, and the
         kernels clamp the offsets to [0, m] (no read past `records`).
+        offs: the headers' episode offsets where the caller has them already
+        (int32 [n + 1] on the device, e.g. ops.canonical_harvest's): the
+        offsets launch is then left out.
         Returns None; asynchronous on the trainer's current stream."""
         import ctypes
         from ._lib import check, lib, ptr, stream_handle
@@ -387,6 +390,10 @@ class DeviceTrainer:
             raise ValueError("update_device: no episodes")
         if n_rec < n_eps or n_rec >= 2 ** 31:
             raise ValueError(f"update_device: {n_eps} episodes cannot hold {n_rec} records")
+        if offs is not None and (not isinstance(offs, torch.Tensor) or offs.dtype != torch.int32 or offs.dim() != 1
+                                 or offs.numel() != n_eps + 1 or offs.device != headers.device
+                                 or not offs.is_contiguous()):
+            raise ValueError("offs must be a contiguous int32 [n + 1] tensor on the headers' device")
         f = self._hip_state()
         dev = f["p"].device
         if self._dev is None or self._dev["metrics"].device != dev:
@@ -404,7 +411,7 @@ class DeviceTrainer:
         # both buffers grow in steps, so a steady state allocates nothing
         if self._work is None or self._work.numel() < need.value or self._work.device != dev:
             self._work = torch.empty(need.value + need.value // 4, dtype=torch.uint8, device=dev)
-        if d["offs"] is None or d["offs"].numel() < n_eps + 1:
+        if offs is None and (d["offs"] is None or d["offs"].numel() < n_eps + 1):
             d["offs"] = torch.empty(2 * (n_eps + 1), dtype=torch.int32, device=dev)
         clip = float(self.grad_clip) if self.grad_clip is not None else 0.0
         lr = float(self.optimizer.param_groups[0]["lr"])
@@ -413,7 +420,8 @@ class DeviceTrainer:
         with torch.cuda.device(dev):   # the trainer's device and its current stream
             s = torch.cuda.current_stream(dev)
             stream = stream_handle(s)
-            offs = ops.episode_offsets(headers, out=d["offs"], stream=s)
+            if offs is None:
+                offs = ops.episode_offsets(headers, out=d["offs"], stream=s)
             if self.afterstates:
                 check(lib().bgx_td_afterstate_update_batched(ptr(records), ptr(headers), ptr(offs), n_eps, n_rec,
                                                              ptr(f["p"]), ptr(f["m"]), ptr(f["v"]), ptr(f["step"]), lr,
