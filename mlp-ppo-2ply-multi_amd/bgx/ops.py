@@ -267,6 +267,63 @@ def episode_offsets(headers, out=None, stream=None):
     return out[:n + 1]
 
 
+TDF_ZERO_SUM = 1   # BGX_TDF_ZERO_SUM (include/bgx.h)
+
+# The batched TD update's entry points (include/bgx.h): each one's workspace
+# query, and which of headers / lam / flags / target_out its signature has
+# beside the arguments all four share.
+TD_BATCHED = {
+    "bgx_td0_update_batched": ("bgx_td0_batch_workspace", ()),
+    "bgx_tdlambda_update_batched": ("bgx_tdlambda_batch_workspace", ("lam", "target_out")),
+    "bgx_td_update_batched": ("bgx_tdlambda_batch_workspace", ("lam", "flags", "target_out")),
+    "bgx_td_afterstate_update_batched": ("bgx_td_afterstate_batch_workspace",
+                                         ("headers", "lam", "flags", "target_out")),
+}
+
+
+def td_batched_entry(lam=0.0, zero_sum=False, afterstates=False):
+    """(entry name, flags) of the batched update that serves a trainer's options:
+    the afterstate entry, else bgx_td_update_batched when zero_sum, else
+    bgx_tdlambda_update_batched when lam != 0, else bgx_td0_update_batched (one
+    launch fewer and no targets in its workspace)."""
+    flags = TDF_ZERO_SUM if zero_sum else 0
+    if afterstates:
+        return "bgx_td_afterstate_update_batched", flags
+    if zero_sum:
+        return "bgx_td_update_batched", flags
+    return ("bgx_tdlambda_update_batched" if lam != 0.0 else "bgx_td0_update_batched"), 0
+
+
+def td_batched_workspace(entry, n_rec):
+    """Bytes of workspace `entry` needs for n_rec records (host arithmetic)."""
+    query = TD_BATCHED[entry][0]
+    need = ctypes.c_uint64(0)
+    check(getattr(lib(), query)(int(n_rec), ctypes.byref(need)), query)
+    return int(need.value)
+
+
+def td_batched_call(entry, *, records, offs, n_eps, n_rec, state, lr, gamma, clip, metrics, work, work_bytes=None,
+                    headers=None, lam=0.0, flags=0, grad_out=None, target_out=None, stream=None):
+    """One call of a batched-update entry point, its named arguments laid out in
+    that entry's positional order; returns the code (td_batched: raises on one).
+    Tensors are contiguous device tensors or None (a null pointer); state = the
+    flat (params, Adam m, Adam v, step). headers, lam, flags and target_out go
+    only to the entries that have them; work_bytes defaults to all of `work`.
+    Asynchronous on the stream (default: the current one)."""
+    has = TD_BATCHED[entry][1]
+    p, m, v, step = state
+    args = [ptr(records)] + ([ptr(headers)] if "headers" in has else []) + \
+           [ptr(offs), int(n_eps), int(n_rec), ptr(p), ptr(m), ptr(v), ptr(step), lr, gamma] + \
+           ([lam] if "lam" in has else []) + ([int(flags)] if "flags" in has else []) + \
+           [clip, ptr(metrics), ptr(grad_out)] + ([ptr(target_out)] if "target_out" in has else []) + \
+           [ptr(work), work.numel() if work_bytes is None else int(work_bytes), stream_handle(stream)]
+    return getattr(lib(), entry)(*args)
+
+
+def td_batched(entry, **kw):
+    check(td_batched_call(entry, **kw), entry)
+
+
 CANON_BITS = {1: "a lane outside [lane_base, lane_base + lanes)", 2: "two episodes share (lane, episode number)",
               4: "the headers' record counts do not sum to the records given"}
 

@@ -74,8 +74,6 @@ import torch.nn.functional as F
 
 from . import ops
 from .records import WIN_TYPES, packed_afterstates
-
-TDF_ZERO_SUM = 1   # BGX_TDF_ZERO_SUM (include/bgx.h)
 from .net import BackgammonPolicyNetwork
 
 LEARNING_RATE = 1e-3          # config/configuration.py:17
@@ -129,11 +127,20 @@ class DeviceTrainer:
         return tile.value, grid.value
 
     # ------------------------------------------------------------ inputs
-    def _from_records(self, headers, records):
-        """(observations [m, 198], rewards [m], episode lengths, win types, movers [m]) on the device."""
+    def _host_inputs(self, headers, records):
+        """What every update_records path starts from: the records as a contiguous
+        int32 device tensor, the headers as host uint32, the episode lengths and
+        their offsets [n + 1] (host int64). The checks are the callers'."""
         rec = torch.as_tensor(records).to(self.device)
         if rec.dtype != torch.int32:
             rec = rec.view(torch.int32) if rec.dtype == torch.uint32 else rec.to(torch.int32)
+        hdr = np.asarray(torch.as_tensor(headers).cpu().numpy()).astype(np.uint32)
+        lens = hdr[:, 3].astype(np.int64)
+        return rec.contiguous(), hdr, lens, np.concatenate([[0], np.cumsum(lens)])
+
+    def _from_records(self, headers, records):
+        """(observations [m, 198], rewards [m], episode lengths, win types, movers [m]) on the device."""
+        rec, hdr, lens, _ = self._host_inputs(headers, records)
         before = torch.zeros((rec.shape[0], 8), dtype=torch.int32, device=self.device)
         if self.afterstates:   # the board after the move, the mover's indicator (records.packed_afterstates)
             rows = packed_afterstates(np.asarray(torch.as_tensor(headers).cpu().numpy()), rec.cpu().numpy())
@@ -142,10 +149,8 @@ class DeviceTrainer:
             before[:, :7] = rec[:, :7]   # the board before the move, the mover's indicator (bgx/records.py)
         obs = ops.encode_packed(before)
         rewards = rec[:, 9].contiguous().view(torch.float32)
-        hdr = np.asarray(torch.as_tensor(headers).cpu().numpy()).astype(np.uint32)
-        lens = hdr[:, 3].astype(np.int64).tolist()
         wins = [WIN_TYPES[int(w) & 0xFF] for w in (hdr[:, 5] & 0xFF).tolist()]
-        return obs, rewards, lens, wins, self._record_movers(rec)
+        return obs, rewards, lens.tolist(), wins, self._record_movers(rec)
 
     @staticmethod
     def _record_movers(rec):
@@ -254,19 +259,13 @@ class DeviceTrainer:
         f["token"] = self._module_token()
 
     def _update_hip(self, headers, records):
-        rec = torch.as_tensor(records).to(self.device)
-        if rec.dtype != torch.int32:
-            rec = rec.view(torch.int32) if rec.dtype == torch.uint32 else rec.to(torch.int32)
-        rec = rec.contiguous()
-        hdr = np.asarray(torch.as_tensor(headers).cpu().numpy()).astype(np.uint32)
-        lens = hdr[:, 3].astype(np.int64)
+        rec, hdr, lens, offs_h = self._host_inputs(headers, records)
         if len(lens) and int(lens.max()) > 2048:
             raise ValueError("bgx_td0_update: an episode has more than 2048 records")
         if len(lens) and int(lens.min()) <= 0:
             # the kernel skips an empty episode (no Adam step), while the metrics
             # below divide by every episode: reject it instead of skewing them
             raise ValueError("bgx_td0_update: an episode has no records")
-        offs_h = np.concatenate([[0], np.cumsum(lens)])
         n_rec = int(rec.shape[0])
         if int(offs_h[-1]) != n_rec or n_rec >= 2 ** 31:
             # the kernel reads records [0, offs[-1]): fewer than that would be read past the tensor's end
@@ -286,69 +285,31 @@ class DeviceTrainer:
         return self._finish_hip(metrics, hdr, lens)
 
     def _update_hip_batched(self, headers, records):
-        """One bgx_td0_update_batched call (bgx_tdlambda_update_batched when
-        lam != 0, bgx_td_update_batched with BGX_TDF_ZERO_SUM when zero_sum,
-        bgx_td_afterstate_update_batched at every lam / zero_sum when afterstates):
-        one Adam step on the mean of the per-episode losses (the torch batched
-        path's semantics)."""
-        import ctypes
-        from ._lib import check, lib, ptr, stream_handle
-        rec = torch.as_tensor(records).to(self.device)
-        if rec.dtype != torch.int32:
-            rec = rec.view(torch.int32) if rec.dtype == torch.uint32 else rec.to(torch.int32)
-        rec = rec.contiguous()
-        hdr = np.asarray(torch.as_tensor(headers).cpu().numpy()).astype(np.uint32)
-        lens = hdr[:, 3].astype(np.int64)
+        """One call of the batched update (the entry point ops.td_batched_entry
+        picks for lam / zero_sum / afterstates): one Adam step on the mean of
+        the per-episode losses (the torch batched path's semantics)."""
+        rec, hdr, lens, offs_h = self._host_inputs(headers, records)
         n_eps, n_rec = len(lens), int(rec.shape[0])
         if n_eps < 1:
             raise ValueError("bgx_td0_update_batched: no episodes")
         if int(lens.min()) <= 0:
             raise ValueError("bgx_td0_update_batched: an episode has no records")
-        offs_h = np.concatenate([[0], np.cumsum(lens)])
         if (np.diff(offs_h) < 1).any() or int(offs_h[-1]) != n_rec or n_rec >= 2 ** 31:
             raise ValueError(f"bgx_td0_update_batched: the headers count {int(offs_h[-1])} records, got {n_rec}")
         offs = torch.as_tensor(offs_h.astype(np.int32), device=self.device)
         f = self._hip_state()
-        need = ctypes.c_uint64(0)
-        if self.afterstates:
-            check(lib().bgx_td_afterstate_batch_workspace(n_rec, ctypes.byref(need)),
-                  "bgx_td_afterstate_batch_workspace")
-        elif self.lam != 0.0 or self.zero_sum:
-            check(lib().bgx_tdlambda_batch_workspace(n_rec, ctypes.byref(need)), "bgx_tdlambda_batch_workspace")
-        else:
-            check(lib().bgx_td0_batch_workspace(n_rec, ctypes.byref(need)), "bgx_td0_batch_workspace")
-        if self._work is None or self._work.numel() < need.value or self._work.device != f["p"].device:
-            self._work = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        entry, flags = ops.td_batched_entry(self.lam, self.zero_sum, self.afterstates)
+        need = ops.td_batched_workspace(entry, n_rec)
+        if self._work is None or self._work.numel() < need or self._work.device != f["p"].device:
+            self._work = torch.empty(need, dtype=torch.uint8, device=self.device)
         metrics = torch.zeros(5, dtype=torch.float64, device=self.device)
-        clip = float(self.grad_clip) if self.grad_clip is not None else 0.0
-        lr = float(self.optimizer.param_groups[0]["lr"])
+        d_hdr = torch.from_numpy(np.ascontiguousarray(hdr).view(np.int32)).to(self.device) if self.afterstates else None
         with torch.cuda.device(self.device):   # the trainer's device and its current stream
-            stream = stream_handle(torch.cuda.current_stream(self.device))
-            if self.afterstates:
-                d_hdr = torch.from_numpy(np.ascontiguousarray(hdr).view(np.int32)).to(self.device)
-                check(lib().bgx_td_afterstate_update_batched(ptr(rec), ptr(d_hdr), ptr(offs), n_eps, n_rec, ptr(f["p"]),
-                                                             ptr(f["m"]), ptr(f["v"]), ptr(f["step"]), lr,
-                                                             float(self.gamma), self.lam,
-                                                             TDF_ZERO_SUM if self.zero_sum else 0, clip, ptr(metrics),
-                                                             None, None, ptr(self._work), self._work.numel(), stream),
-                      "bgx_td_afterstate_update_batched")
-            elif self.zero_sum:
-                check(lib().bgx_td_update_batched(ptr(rec), ptr(offs), n_eps, n_rec, ptr(f["p"]), ptr(f["m"]),
-                                                  ptr(f["v"]), ptr(f["step"]), lr, float(self.gamma), self.lam,
-                                                  TDF_ZERO_SUM, clip, ptr(metrics), None, None, ptr(self._work),
-                                                  self._work.numel(), stream),
-                      "bgx_td_update_batched")
-            elif self.lam != 0.0:
-                check(lib().bgx_tdlambda_update_batched(ptr(rec), ptr(offs), n_eps, n_rec, ptr(f["p"]), ptr(f["m"]),
-                                                        ptr(f["v"]), ptr(f["step"]), lr, float(self.gamma), self.lam,
-                                                        clip, ptr(metrics), None, None, ptr(self._work),
-                                                        self._work.numel(), stream),
-                      "bgx_tdlambda_update_batched")
-            else:
-                check(lib().bgx_td0_update_batched(ptr(rec), ptr(offs), n_eps, n_rec, ptr(f["p"]), ptr(f["m"]),
-                                                   ptr(f["v"]), ptr(f["step"]), lr, float(self.gamma), clip,
-                                                   ptr(metrics), None, ptr(self._work), self._work.numel(), stream),
-                      "bgx_td0_update_batched")
+            ops.td_batched(entry, records=rec, headers=d_hdr, offs=offs, n_eps=n_eps, n_rec=n_rec,
+                           state=(f["p"], f["m"], f["v"], f["step"]), lr=float(self.optimizer.param_groups[0]["lr"]),
+                           gamma=float(self.gamma), lam=self.lam, flags=flags,
+                           clip=float(self.grad_clip) if self.grad_clip is not None else 0.0, metrics=metrics,
+                           work=self._work, stream=torch.cuda.current_stream(self.device))
         return self._finish_hip(metrics, hdr, lens)
 
     # ------------------------------------------------------------ device-resident update
@@ -359,7 +320,7 @@ class DeviceTrainer:
         (Engine.harvest_fetch(clone=False)). Needs batched=True and
         backend="hip". No tensor is read on the host: the offsets come from
         ops.episode_offsets, n and m from the shapes, the ABI call is the one
-        _update_hip_batched chooses (the headers go in as d_headers), and the
+        _update_hip_batched makes (the headers go in as d_headers), and the
         five metrics add up in a device tensor the trainer owns. The torch
         module, the optimizer and the parameter manager are not touched:
         metrics(), sync_module(), state_dict() and publish() bring the host up
@@ -374,8 +335,6 @@ class DeviceTrainer:
         (int32 [n + 1] on the device, e.g. ops.canonical_harvest's): the
         offsets launch is then left out.
         Returns None; asynchronous on the trainer's current stream."""
-        import ctypes
-        from ._lib import check, lib, ptr, stream_handle
         if not (self.batched and self.backend == "hip"):
             raise ValueError("update_device needs batched=True and backend='hip' (the batched HIP update is the only "
                              "one that runs without the host)")
@@ -400,52 +359,22 @@ class DeviceTrainer:
             self._dev = {"metrics": torch.zeros(5, dtype=torch.float64, device=dev), "offs": None,
                          "updates": 0, "episodes": 0, "records": 0}
         d = self._dev
-        need = ctypes.c_uint64(0)
-        if self.afterstates:
-            check(lib().bgx_td_afterstate_batch_workspace(n_rec, ctypes.byref(need)),
-                  "bgx_td_afterstate_batch_workspace")
-        elif self.lam != 0.0 or self.zero_sum:
-            check(lib().bgx_tdlambda_batch_workspace(n_rec, ctypes.byref(need)), "bgx_tdlambda_batch_workspace")
-        else:
-            check(lib().bgx_td0_batch_workspace(n_rec, ctypes.byref(need)), "bgx_td0_batch_workspace")
+        entry, flags = ops.td_batched_entry(self.lam, self.zero_sum, self.afterstates)
+        need = ops.td_batched_workspace(entry, n_rec)
         # both buffers grow in steps, so a steady state allocates nothing
-        if self._work is None or self._work.numel() < need.value or self._work.device != dev:
-            self._work = torch.empty(need.value + need.value // 4, dtype=torch.uint8, device=dev)
+        if self._work is None or self._work.numel() < need or self._work.device != dev:
+            self._work = torch.empty(need + need // 4, dtype=torch.uint8, device=dev)
         if offs is None and (d["offs"] is None or d["offs"].numel() < n_eps + 1):
             d["offs"] = torch.empty(2 * (n_eps + 1), dtype=torch.int32, device=dev)
-        clip = float(self.grad_clip) if self.grad_clip is not None else 0.0
-        lr = float(self.optimizer.param_groups[0]["lr"])
-        gamma = self._gamma_host
-        metrics = d["metrics"]
         with torch.cuda.device(dev):   # the trainer's device and its current stream
             s = torch.cuda.current_stream(dev)
-            stream = stream_handle(s)
             if offs is None:
                 offs = ops.episode_offsets(headers, out=d["offs"], stream=s)
-            if self.afterstates:
-                check(lib().bgx_td_afterstate_update_batched(ptr(records), ptr(headers), ptr(offs), n_eps, n_rec,
-                                                             ptr(f["p"]), ptr(f["m"]), ptr(f["v"]), ptr(f["step"]), lr,
-                                                             gamma, self.lam, TDF_ZERO_SUM if self.zero_sum else 0,
-                                                             clip, ptr(metrics), None, None, ptr(self._work),
-                                                             self._work.numel(), stream),
-                      "bgx_td_afterstate_update_batched")
-            elif self.zero_sum:
-                check(lib().bgx_td_update_batched(ptr(records), ptr(offs), n_eps, n_rec, ptr(f["p"]), ptr(f["m"]),
-                                                  ptr(f["v"]), ptr(f["step"]), lr, gamma, self.lam, TDF_ZERO_SUM, clip,
-                                                  ptr(metrics), None, None, ptr(self._work), self._work.numel(),
-                                                  stream),
-                      "bgx_td_update_batched")
-            elif self.lam != 0.0:
-                check(lib().bgx_tdlambda_update_batched(ptr(records), ptr(offs), n_eps, n_rec, ptr(f["p"]), ptr(f["m"]),
-                                                        ptr(f["v"]), ptr(f["step"]), lr, gamma, self.lam, clip,
-                                                        ptr(metrics), None, None, ptr(self._work), self._work.numel(),
-                                                        stream),
-                      "bgx_tdlambda_update_batched")
-            else:
-                check(lib().bgx_td0_update_batched(ptr(records), ptr(offs), n_eps, n_rec, ptr(f["p"]), ptr(f["m"]),
-                                                   ptr(f["v"]), ptr(f["step"]), lr, gamma, clip, ptr(metrics), None,
-                                                   ptr(self._work), self._work.numel(), stream),
-                      "bgx_td0_update_batched")
+            ops.td_batched(entry, records=records, headers=headers, offs=offs, n_eps=n_eps, n_rec=n_rec,
+                           state=(f["p"], f["m"], f["v"], f["step"]), lr=float(self.optimizer.param_groups[0]["lr"]),
+                           gamma=self._gamma_host, lam=self.lam, flags=flags,
+                           clip=float(self.grad_clip) if self.grad_clip is not None else 0.0, metrics=d["metrics"],
+                           work=self._work, stream=s)
         d["updates"] += 1
         d["episodes"] += n_eps
         d["records"] += n_rec

@@ -340,12 +340,17 @@ int bgx_td0_update(const uint32_t* d_records, const int32_t* d_offs, int n_eps, 
     });
 }
 
-int bgx_td0_batch_workspace(int n_records, uint64_t* bytes) {
-    return guarded("bgx_td0_batch_workspace", [&]() -> int {
-        if (n_records <= 0 || !bytes) return fail(BGX_E_ARG, "bgx_td0_batch_workspace: n_records=%d", n_records);
-        *bytes = bgx::train_batch_layout(n_records).bytes;
+// the three workspace queries: `size` is the entry's total in the layout
+static int batch_workspace(const char* name, uint64_t bgx::TrainBatchLayout::*size, int n_records, uint64_t* bytes) {
+    return guarded(name, [&]() -> int {
+        if (n_records <= 0 || !bytes) return fail(BGX_E_ARG, "%s: n_records=%d", name, n_records);
+        *bytes = bgx::train_batch_layout(n_records).*size;
         return BGX_OK;
     });
+}
+
+int bgx_td0_batch_workspace(int n_records, uint64_t* bytes) {
+    return batch_workspace("bgx_td0_batch_workspace", &bgx::TrainBatchLayout::bytes, n_records, bytes);
 }
 
 int bgx_td0_batch_shape(int* tile, int* grid) {
@@ -412,14 +417,10 @@ static int update_batched(const char* name, bool lam, bool after, const uint32_t
             a.zero_sum = (flags & BGX_TDF_ZERO_SUM) ? 1 : 0;
         }
         if (after) {
-            bgx::TrainAfterBatchArgs x{};
-            static_cast<bgx::TrainBatchArgs&>(x) = a;
-            x.hdr = d_headers;
-            x.srcidx = (int32_t*)(w + l.srcidx);
-            HIP_TRY(bgx_launch_td_after_batched(&x, (hipStream_t)stream));
-            return BGX_OK;
+            a.hdr = d_headers;
+            a.srcidx = (int32_t*)(w + l.srcidx);
         }
-        HIP_TRY(bgx_launch_td0_batched(&a, (hipStream_t)stream));
+        HIP_TRY(bgx_launch_td_batched(&a, (hipStream_t)stream));
         return BGX_OK;
     });
 }
@@ -434,11 +435,7 @@ int bgx_td0_update_batched(const uint32_t* d_records, const int32_t* d_offs, int
 }
 
 int bgx_tdlambda_batch_workspace(int n_records, uint64_t* bytes) {
-    return guarded("bgx_tdlambda_batch_workspace", [&]() -> int {
-        if (n_records <= 0 || !bytes) return fail(BGX_E_ARG, "bgx_tdlambda_batch_workspace: n_records=%d", n_records);
-        *bytes = bgx::train_batch_layout(n_records).bytes_lambda;
-        return BGX_OK;
-    });
+    return batch_workspace("bgx_tdlambda_batch_workspace", &bgx::TrainBatchLayout::bytes_lambda, n_records, bytes);
 }
 
 int bgx_tdlambda_update_batched(const uint32_t* d_records, const int32_t* d_offs, int n_eps, int n_records,
@@ -460,12 +457,7 @@ int bgx_td_update_batched(const uint32_t* d_records, const int32_t* d_offs, int 
 }
 
 int bgx_td_afterstate_batch_workspace(int n_records, uint64_t* bytes) {
-    return guarded("bgx_td_afterstate_batch_workspace", [&]() -> int {
-        if (n_records <= 0 || !bytes)
-            return fail(BGX_E_ARG, "bgx_td_afterstate_batch_workspace: n_records=%d", n_records);
-        *bytes = bgx::train_batch_layout(n_records).bytes_after;
-        return BGX_OK;
-    });
+    return batch_workspace("bgx_td_afterstate_batch_workspace", &bgx::TrainBatchLayout::bytes_after, n_records, bytes);
 }
 
 int bgx_td_afterstate_update_batched(const uint32_t* d_records, const uint32_t* d_headers, const int32_t* d_offs,

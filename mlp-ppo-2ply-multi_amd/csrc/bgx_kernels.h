@@ -294,10 +294,13 @@ struct TrainArgs {
     double* metrics;             // [5] += loss, post-clip grad norm, |td| mean, V mean, reward sum (per episode)
 };
 
-// Batched TD(0) update (bgx_train_batch.hip): one Adam step per call on the mean
-// of the per-episode losses, over all CUs. The workspace (TrainBatchLayout) holds
-// Y and the episode info of every record, one partial gradient per workgroup of
-// the largest grid, the summed gradient and the launches' partial sums.
+// Batched TD update (bgx_train_batch.hip): one Adam step per call on the mean
+// of the per-episode losses, over all CUs. One struct for all four entry points
+// (bgx_td0_, bgx_tdlambda_, bgx_td_ and bgx_td_afterstate_update_batched): the
+// TD(0) update and its three options, each switched on by its own fields. The
+// workspace (TrainBatchLayout) holds Y and the episode info of every record, one
+// partial gradient per workgroup of the largest grid, the summed gradient and
+// the launches' partial sums; then the options' parts, tgt and srcidx.
 constexpr int TRAIN_BATCH_TILE = 128;        // records per backward tile
 constexpr int TRAIN_BATCH_GRID = 256;        // most workgroups a forward / backward launch has
 constexpr int TRAIN_BATCH_PARAMS = 25601;    // 128 * 198 + 128 + 128 + 1
@@ -329,10 +332,8 @@ struct TrainBatchArgs {
     // zero-sum targets (bgx_td_update_batched, BGX_TDF_ZERO_SUM; needs tgt): the next record's Y and G
     // enter as 1 - x where the mover (word 11 bit 9) changes; the target stage then runs at every lambda
     int zero_sum;
-};
-// TrainBatchArgs for afterstate rows (bgx_td_afterstate_update_batched; bgx_train_tile.h). The base keeps
-// its layout: the kernels that know no afterstates take it as it was
-struct TrainAfterBatchArgs : TrainBatchArgs {
+    // afterstate rows (bgx_td_afterstate_update_batched; bgx_train_tile.h; needs tgt); both null: the
+    // records' own before-move rows
     const uint32_t* hdr;         // [n_eps][16] episode headers: words 6..12, the final board, are read
     int32_t* srcidx;             // workspace [n_rec]: where a record's row comes from (tb_index<true>)
 };
@@ -399,9 +400,9 @@ hipError_t bgx_launch_top5(const float* V, const int32_t* job_off, const int32_t
                                                                      // (bgx::T5_WAVES slots, or null)
 hipError_t bgx_launch_two_ply_reduce(const float* job_val, int n, double* out, hipStream_t stream);
 hipError_t bgx_launch_td0(const bgx::TrainArgs* args, hipStream_t stream);
-hipError_t bgx_launch_td0_batched(const bgx::TrainBatchArgs* args, hipStream_t stream);
-// the same on afterstate rows; args->tgt must be set (the backward launch reads the target stage's G)
-hipError_t bgx_launch_td_after_batched(const bgx::TrainAfterBatchArgs* args, hipStream_t stream);
+// the batched update; args->hdr / srcidx set: on afterstate rows, and args->tgt must be set too (the
+// backward launch then reads the target stage's G)
+hipError_t bgx_launch_td_batched(const bgx::TrainBatchArgs* args, hipStream_t stream);
 // tgt[s] (and target_out[s]) = the lambda-return of every record in an episode, 0 elsewhere;
 // reads Y, so it goes between the forward and the backward launch (bgx_train_lambda.hip)
 hipError_t bgx_launch_lambda_targets(const bgx::TrainBatchArgs* args, hipStream_t stream);

@@ -1,9 +1,11 @@
-// bgx_train_batch.hip — the batched TD(0) update (DeviceTrainer batched=True) on
+// bgx_train_batch.hip — the batched TD update (DeviceTrainer batched=True) on
 // the whole GPU: ONE Adam step per call on the mean of the per-episode losses,
 //   loss = (1/E) sum_e (1/T_e) sum_s (Y_s - tgt_s)^2,
 //   tgt_s = r_s + gamma Y_{s+1} (detached; r_s alone on an episode's last record),
 // where bgx_train.hip walks the episodes one after another in one workgroup.
 //
+// One launcher (bgx_launch_td_batched) and one argument struct (TrainBatchArgs)
+// serve the four entry points: the TD(0) update below and its three options.
 // Five launches on the caller's stream, no host synchronisation:
 //   index     one thread per episode: info[s] = T_e | last << 31 for its records
 //             (offs clamped to [0, n_records]; a record in no episode keeps 0 and
@@ -20,11 +22,14 @@
 //   adam      norm, clip coefficient and the Adam step over the parameters
 // Every sum has a fixed order (no float atomics): the same inputs give the same
 // bits on every call.
-// bgx_tdlambda_update_batched (TrainBatchArgs::tgt set) is the same call with the
-// lambda-return as the target: the target stage of bgx_train_lambda.hip runs
-// between forward and backward, and the backward launch reads tgt[s].
-// bgx_td_update_batched with BGX_TDF_ZERO_SUM (TrainBatchArgs::zero_sum) is that
-// call with the stage's zero-sum instance, at every lambda.
+// The options:
+//   TrainBatchArgs::tgt (bgx_tdlambda_update_batched): the lambda-return as the
+//   target. The target stage of bgx_train_lambda.hip runs between forward and
+//   backward, and the backward launch reads tgt[s] (its LAM instance).
+//   TrainBatchArgs::zero_sum (bgx_td_update_batched with BGX_TDF_ZERO_SUM): the
+//   stage's zero-sum instance, at every lambda.
+//   TrainBatchArgs::hdr / srcidx (bgx_td_afterstate_update_batched): afterstate
+//   rows, the AFTER instances of the index, forward and backward kernels (below).
 //
 // Both GEMMs run on the f32-input MFMA (v_mfma_f32_32x32x2_f32: an exact k-ordered
 // fp32 fma chain, so no weight scaling and no dh underflow). A workgroup is 4
@@ -39,20 +44,18 @@
 //             so register t of chunk c IS the A operand of a k-step over the two
 //             records 32 c + row(t, lane half) with no lane movement and no LDS;
 //             B = the feature nt * 32 + (lane & 31) of those two records, from
-//             the tile's packed words and a [224][16] nibble -> value table in LDS (rows of 17 words).
+//             the tile's packed words (the feature's field, tb_field) and a [224][16]
+//             field value -> feature value table in LDS (tb_lut_entry; rows of 17 words).
 //             7 accumulator tiles (224 >= 198 features) per wave.
 // Nothing episode-sized lives in LDS: no episode-length limit.
 //
-// bgx_td_afterstate_update_batched is bgx_td_update_batched on afterstate rows: V
-// is fitted on the board each mover leaves, under the mover's indicator, the
-// positions the engine rates. The index, forward and backward kernels are
-// templates on their argument struct; with TrainAfterBatchArgs the index launch
-// also writes where each record's row comes from (the next record, or the episode
-// header's final board) and the forward and backward launches load those rows
+// Afterstate rows: V is fitted on the board each mover leaves, under the mover's
+// indicator, the positions the engine rates. The index, forward and backward
+// kernels are templates on AFTER; with it the index launch also writes where
+// each record's row comes from (the next record, or the episode header's final
+// board) and the forward and backward launches load those rows
 // (bgx_train_tile.h). Nothing else differs: everything downstream of the loader
 // is the same code, and the backward launch always reads the target stage's G.
-#include <type_traits>
-
 #include "bgx_device.h"
 #include "bgx_kernels.h"
 #include "bgx_train_tile.h"
@@ -72,20 +75,6 @@ constexpr int TB_NB = (TB_NP + TB_T - 1) / TB_T;   // blocks of the reduce / ada
 static_assert(TB_NB <= TRAIN_BATCH_SQ, "sum-of-squares slots");
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// the value of live feature k (immutable_board.py:86-128) as a function of the
-// field it reads: a point's checker count, a bar / off count, or the indicator bit
-BGX_DEV float tb_lut_entry(int k, int n) {
-    if (k >= 198) return 0.0f;
-    if (k >= 196) return n == k - 196 ? 1.0f : 0.0f;
-    if (k >= 192) return (k & 1) ? (float)((double)n / 15.0) : (float)n * 0.5f;
-    switch (k & 3) {
-        case 0: return n >= 1 ? 1.0f : 0.0f;
-        case 1: return n >= 2 ? 1.0f : 0.0f;
-        case 2: return n >= 3 ? 1.0f : 0.0f;
-        default: return n > 3 ? (float)(n - 3) * 0.5f : 0.0f;
-    }
-}
 
 // features 2 S (lane half 0) and 2 S + 1 (lane half 1) of packed words wd[0..6];
 // off1 / off2 = the lane's borne-off features 193 / 195 (the table's values)
@@ -111,14 +100,11 @@ BGX_DEV float tb_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 // accumulator register t of lane half h holds row (record) ...
 BGX_DEV constexpr int tb_row(int t, int h) { return (t & 3) + 8 * (t >> 2) + 4 * h; }
 
-template <class Args>
-constexpr bool tb_after = std::is_same_v<Args, TrainAfterBatchArgs>;
-
 // the tile's rows into LDS: the records' own words, or their afterstate rows
 // (SRC: the tile's source indices, bgx_train_tile.h)
-template <class Args>
-BGX_DEV void tb_load_rows(const Args& a, const int32_t* SRC, long long base, uint32_t (*RW)[8]) {
-    if constexpr (tb_after<Args>) tb_load_tile_after(a.rec, a.hdr, SRC, a.n_rec, base, RW);
+template <bool AFTER>
+BGX_DEV void tb_load_rows(const TrainBatchArgs& a, const int32_t* SRC, long long base, uint32_t (*RW)[8]) {
+    if constexpr (AFTER) tb_load_tile_after(a.rec, a.hdr, SRC, a.n_rec, base, RW);
     else tb_load_tile(a.rec, a.n_rec, base, RW);
 }
 
@@ -198,15 +184,14 @@ BGX_DEV double tb_block_sum(double v, double* red) {
 }  // namespace
 
 // ---------------------------------------------------------------- index
-template <class Args>
-__global__ __launch_bounds__(TB_T) void tb_index_kernel(Args a) {
-    if constexpr (tb_after<Args>) tb_index<true>(a, a.srcidx);
-    else tb_index<false>(a, nullptr);
+template <bool AFTER>
+__global__ __launch_bounds__(TB_T) void tb_index_kernel(TrainBatchArgs a) {
+    tb_index<AFTER>(a);
 }
 
 // ---------------------------------------------------------------- forward
-template <class Args>
-__global__ __launch_bounds__(TB_T) void tb_forward_kernel(Args a) {
+template <bool AFTER>
+__global__ __launch_bounds__(TB_T) void tb_forward_kernel(TrainBatchArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t RW[TB_TILE][8];
     __shared__ float P[TB_TILE][65];    // w2_j S[record][j], units j and j + 16 of a wave summed (65: conflict-free columns)
     __shared__ float off15[16];
@@ -218,14 +203,14 @@ __global__ __launch_bounds__(TB_T) void tb_forward_kernel(Args a) {
     const float b1v = a.params[TB_NW1 + unit], w2v = a.params[TB_NW1 + 128 + unit];
     const float b2 = a.params[TB_NW1 + 256];
     __shared__ int32_t SRC[TB_TILE];   // afterstate rows only
-    if constexpr (tb_after<Args>) tb_stage_src(a.srcidx, a.n_rec, (long long)blockIdx.x * TB_TILE, SRC);
+    if constexpr (AFTER) tb_stage_src(a.srcidx, a.n_rec, (long long)blockIdx.x * TB_TILE, SRC);
     for (int tile = (int)blockIdx.x; tile < a.n_tiles; tile += (int)gridDim.x) {
         const long long base = (long long)tile * TB_TILE;
-        if constexpr (tb_after<Args>) __builtin_amdgcn_s_waitcnt(0xF70);   // vmcnt(0): the requested SRC entries are in LDS
+        if constexpr (AFTER) __builtin_amdgcn_s_waitcnt(0xF70);   // vmcnt(0): the requested SRC entries are in LDS
         __syncthreads();   // the previous tile's P / RW readers are done
-        tb_load_rows(a, SRC, base, RW);
+        tb_load_rows<AFTER>(a, SRC, base, RW);
         __syncthreads();
-        if constexpr (tb_after<Args>)   // the next tile's, under this tile's MFMA chains
+        if constexpr (AFTER)   // the next tile's, under this tile's MFMA chains
             tb_stage_src(a.srcidx, a.n_rec, base + (long long)gridDim.x * TB_TILE, SRC);
         f32x16 acc[TB_C];
         tb_forward(W, b1v, RW, off15, lane, acc);
@@ -248,8 +233,8 @@ __global__ __launch_bounds__(TB_T) void tb_forward_kernel(Args a) {
 
 // ---------------------------------------------------------------- backward
 // LAM: the target is the target stage's tgt[s] (TD(lambda)), not the inline TD(0) one
-template <bool LAM, class Args>
-__global__ __launch_bounds__(TB_T) void tb_backward_kernel(Args a) {
+template <bool LAM, bool AFTER>
+__global__ __launch_bounds__(TB_T) void tb_backward_kernel(TrainBatchArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t RW[TB_TILE][8];
     __shared__ __attribute__((aligned(16))) float D[TB_TILE];   // dL/dY of the tile's records
     __shared__ float LUT[32 * TB_NT][TB_LUTW];   // rows padded to 17: a lane per row, conflict-free
@@ -265,22 +250,10 @@ __global__ __launch_bounds__(TB_T) void tb_backward_kernel(Args a) {
     int fw[TB_NT], fsh[TB_NT], fmask[TB_NT];
 #pragma unroll
     for (int nt = 0; nt < TB_NT; ++nt) {
-        const int k = 32 * nt + (lane & 31);
-        if (k < 192) {
-            const int pl = k / 96, i = (k - 96 * pl) >> 2;
-            fw[nt] = 3 * pl + (i >> 3);
-            fsh[nt] = (i & 7) * 4;
-            fmask[nt] = 15;
-        } else if (k < 196) {
-            const int q = k - 192;
-            fw[nt] = 6;
-            fsh[nt] = 4 * (q >> 1) + ((q & 1) ? 8 : 0);
-            fmask[nt] = 15;
-        } else {
-            fw[nt] = 6;
-            fsh[nt] = 16;
-            fmask[nt] = k < 198 ? 1 : 0;
-        }
+        const TbField fd = tb_field(32 * nt + (lane & 31));
+        fw[nt] = fd.word;
+        fsh[nt] = fd.shift;
+        fmask[nt] = fd.mask;
     }
     f32x16 dW[TB_NT];
 #pragma unroll
@@ -291,13 +264,13 @@ __global__ __launch_bounds__(TB_T) void tb_backward_kernel(Args a) {
     double m_loss = 0.0, m_td = 0.0, m_y = 0.0, m_rw = 0.0;   // threads < TB_TILE: their records' shares
     const float n_eps = (float)a.n_eps;
     __shared__ int32_t SRC[TB_TILE];   // afterstate rows only
-    if constexpr (tb_after<Args>) tb_stage_src(a.srcidx, a.n_rec, (long long)blockIdx.x * TB_TILE, SRC);
+    if constexpr (AFTER) tb_stage_src(a.srcidx, a.n_rec, (long long)blockIdx.x * TB_TILE, SRC);
 
     for (int tile = (int)blockIdx.x; tile < a.n_tiles; tile += (int)gridDim.x) {
         const long long base = (long long)tile * TB_TILE;
-        if constexpr (tb_after<Args>) __builtin_amdgcn_s_waitcnt(0xF70);   // vmcnt(0): the requested SRC entries are in LDS
+        if constexpr (AFTER) __builtin_amdgcn_s_waitcnt(0xF70);   // vmcnt(0): the requested SRC entries are in LDS
         __syncthreads();   // the previous tile's readers are done
-        tb_load_rows(a, SRC, base, RW);
+        tb_load_rows<AFTER>(a, SRC, base, RW);
         if (t < TB_TILE) {
             const long long s = base + t;
             float d = 0.0f;
@@ -324,7 +297,7 @@ __global__ __launch_bounds__(TB_T) void tb_backward_kernel(Args a) {
             D[t] = d;
         }
         __syncthreads();
-        if constexpr (tb_after<Args>)   // the next tile's, under this tile's MFMA chains
+        if constexpr (AFTER)   // the next tile's, under this tile's MFMA chains
             tb_stage_src(a.srcidx, a.n_rec, base + (long long)gridDim.x * TB_TILE, SRC);
         f32x16 acc[TB_C];
         tb_forward(W, b1v, RW, off15, lane, acc);
@@ -447,52 +420,40 @@ __global__ __launch_bounds__(TB_T) void tb_adam_kernel(TrainBatchArgs a) {
 
 }  // namespace bgx
 
-extern "C" hipError_t bgx_launch_td0_batched(const bgx::TrainBatchArgs* args, hipStream_t stream) {
+// The launch sequence of every entry point. The target stage runs when the
+// backward launch reads its targets (lam below) or the caller wants them
+// (target_out); the records' movers and rewards it reads (words 11 and 9) are
+// the same under AFTER.
+template <bool AFTER>
+static hipError_t tb_launch(bgx::TrainBatchArgs a, hipStream_t stream) {
     using namespace bgx;
-    TrainBatchArgs a = *args;
     a.n_tiles = (int)(((long long)a.n_rec + TB_TILE - 1) / TB_TILE);
     a.grid = a.n_tiles < TRAIN_BATCH_GRID ? a.n_tiles : TRAIN_BATCH_GRID;
+    // a record in no episode keeps 0 in both: it takes no part, its row is its own words
     hipError_t e = hipMemsetAsync(a.info, 0, (size_t)a.n_rec * sizeof(int32_t), stream);
+    if (AFTER && e == hipSuccess) e = hipMemsetAsync(a.srcidx, 0, (size_t)a.n_rec * sizeof(int32_t), stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(tb_index_kernel<TrainBatchArgs>, dim3((a.n_eps + TB_T - 1) / TB_T), dim3(TB_T), 0, stream, a);
-    hipLaunchKernelGGL(tb_forward_kernel<TrainBatchArgs>, dim3(a.grid), dim3(TB_T), 0, stream, a);
-    // TD(lambda): the target stage, then the backward launch on its targets. lambda = 0
-    // keeps the TD(0) backward launch (the same bits by construction); the stage then
-    // runs only to fill target_out. Zero-sum targets: the inline TD(0) target knows no
-    // movers, so the stage and the backward launch on its targets run at lambda = 0 too
+    hipLaunchKernelGGL(tb_index_kernel<AFTER>, dim3((a.n_eps + TB_T - 1) / TB_T), dim3(TB_T), 0, stream, a);
+    hipLaunchKernelGGL(tb_forward_kernel<AFTER>, dim3(a.grid), dim3(TB_T), 0, stream, a);
+    // lambda = 0 keeps the TD(0) backward launch (the same bits by construction); the
+    // stage then runs only to fill target_out. Zero-sum targets: the inline TD(0)
+    // target knows no movers, so the stage and the backward launch on its targets
+    // run at lambda = 0 too. Afterstates: always both
     if (!a.tgt) a.zero_sum = 0;
-    const bool lam = a.tgt && (a.lambda != 0.0f || a.zero_sum);
+    const bool lam = AFTER || (a.tgt && (a.lambda != 0.0f || a.zero_sum));
     if (lam || (a.tgt && a.target_out)) {
         e = bgx_launch_lambda_targets(&a, stream);
         if (e != hipSuccess) return e;
     }
-    if (lam) hipLaunchKernelGGL((tb_backward_kernel<true, TrainBatchArgs>), dim3(a.grid), dim3(TB_T), 0, stream, a);
-    else hipLaunchKernelGGL((tb_backward_kernel<false, TrainBatchArgs>), dim3(a.grid), dim3(TB_T), 0, stream, a);
+    if (lam) hipLaunchKernelGGL((tb_backward_kernel<true, AFTER>), dim3(a.grid), dim3(TB_T), 0, stream, a);
+    else if constexpr (!AFTER) hipLaunchKernelGGL((tb_backward_kernel<false, false>), dim3(a.grid), dim3(TB_T), 0, stream, a);
     hipLaunchKernelGGL(tb_reduce_kernel, dim3(TB_NB), dim3(TB_T), 0, stream, a);
     hipLaunchKernelGGL(tb_adam_kernel, dim3(TB_NB), dim3(TB_T), 0, stream, a);
     return hipGetLastError();
 }
 
-// the same launches on afterstate rows (bgx_train_tile.h): the index launch also
-// fills srcidx, the target stage runs at every lambda and flag, untouched (it
-// reads movers and rewards from record words 11 and 9, which afterstates do not
-// alter), and the backward launch reads its targets
-extern "C" hipError_t bgx_launch_td_after_batched(const bgx::TrainAfterBatchArgs* args, hipStream_t stream) {
-    using namespace bgx;
-    TrainAfterBatchArgs a = *args;
-    if (!a.tgt || !a.hdr || !a.srcidx) return hipErrorInvalidValue;
-    a.n_tiles = (int)(((long long)a.n_rec + TB_TILE - 1) / TB_TILE);
-    a.grid = a.n_tiles < TRAIN_BATCH_GRID ? a.n_tiles : TRAIN_BATCH_GRID;
-    hipError_t e = hipMemsetAsync(a.info, 0, (size_t)a.n_rec * sizeof(int32_t), stream);
-    if (e == hipSuccess) e = hipMemsetAsync(a.srcidx, 0, (size_t)a.n_rec * sizeof(int32_t), stream);
-    if (e != hipSuccess) return e;
-    const TrainBatchArgs& b = a;   // the launches that know no afterstates
-    hipLaunchKernelGGL(tb_index_kernel<TrainAfterBatchArgs>, dim3((a.n_eps + TB_T - 1) / TB_T), dim3(TB_T), 0, stream, a);
-    hipLaunchKernelGGL(tb_forward_kernel<TrainAfterBatchArgs>, dim3(a.grid), dim3(TB_T), 0, stream, a);
-    e = bgx_launch_lambda_targets(&b, stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((tb_backward_kernel<true, TrainAfterBatchArgs>), dim3(a.grid), dim3(TB_T), 0, stream, a);
-    hipLaunchKernelGGL(tb_reduce_kernel, dim3(TB_NB), dim3(TB_T), 0, stream, b);
-    hipLaunchKernelGGL(tb_adam_kernel, dim3(TB_NB), dim3(TB_T), 0, stream, b);
-    return hipGetLastError();
+extern "C" hipError_t bgx_launch_td_batched(const bgx::TrainBatchArgs* args, hipStream_t stream) {
+    if (!args->hdr && !args->srcidx) return tb_launch<false>(*args, stream);
+    if (!args->tgt || !args->hdr || !args->srcidx) return hipErrorInvalidValue;
+    return tb_launch<true>(*args, stream);
 }

@@ -1,6 +1,8 @@
-// bgx_train_tile.h — the index launch and the tile loaders of the batched update
-// (bgx_train_batch.hip), apart from the MFMA code so that the host emulation
-// (tests/cpuwave/after_emu.cpp) compiles them alone: plain loads and stores.
+// bgx_train_tile.h — what the trainer units share apart from the MFMA code, so
+// that the host emulation (tests/cpuwave/after_emu.cpp, feature_emu.cpp)
+// compiles it alone, plain loads and stores: the live-feature rule of the batched
+// backward kernel (tb_field, tb_lut_entry), the index launch and the tile
+// loaders of the batched update (bgx_train_batch.hip).
 //
 // Afterstate rows (bgx_td_afterstate_update_batched). The row of record s of an
 // episode [a, b) is the board the mover leaves, under the mover's indicator:
@@ -32,10 +34,48 @@ namespace bgx {
 constexpr int TB_T = 256;                          // threads of every launch of the batched update
 constexpr int TB_TILE = TRAIN_BATCH_TILE;          // records per tile
 
+// The live encoding (immutable_board.py:86-128) of packed words w[0..6], in two
+// steps: the field that feature k reads, n = (w[word] >> shift) & mask (a point's
+// checker count, a bar / off count, or the indicator bit; k >= 198: mask 0), and
+// the feature's value as a function of n.
+struct TbField {
+    int word, shift, mask;
+};
+BGX_DEV TbField tb_field(int k) {
+    if (k < 192) {
+        const int pl = k / 96, i = (k - 96 * pl) >> 2;
+        return {3 * pl + (i >> 3), (i & 7) * 4, 15};
+    }
+    if (k < 196) {   // bar1, off1, bar2, off2
+        const int q = k - 192;
+        return {6, 4 * (q >> 1) + ((q & 1) ? 8 : 0), 15};
+    }
+    return {6, 16, k < 198 ? 1 : 0};
+}
+BGX_DEV float tb_lut_entry(int k, int n) {
+    if (k >= 198) return 0.0f;
+    if (k >= 196) return n == k - 196 ? 1.0f : 0.0f;
+    if (k >= 192) return (k & 1) ? (float)((double)n / 15.0) : (float)n * 0.5f;
+    switch (k & 3) {
+        case 0: return n >= 1 ? 1.0f : 0.0f;
+        case 1: return n >= 2 ? 1.0f : 0.0f;
+        case 2: return n >= 3 ? 1.0f : 0.0f;
+        default: return n > 3 ? (float)(n - 3) * 0.5f : 0.0f;
+    }
+}
+// feature f of packed words w[0..6]: the two composed. bgx_train.hip's
+// live_feature states the same rule in one function of its own: as this
+// composition its chunk loader compiled to a sequential kernel 2.4 % slower
+// (profiles/train_refactor/README.md)
+BGX_DEV float tb_feature(const uint32_t* w, int f) {
+    const TbField fd = tb_field(f);
+    return tb_lut_entry(f, (int)((w[fd.word] >> fd.shift) & (uint32_t)fd.mask));
+}
+
 // one thread per episode: info[s] = T_e | last << 31 for its records (offs
 // clamped to [0, n_rec]), the Adam step count + 1; AFTER: srcidx[s] as above
 template <bool AFTER>
-BGX_DEV void tb_index(const TrainBatchArgs& a, int32_t* srcidx) {
+BGX_DEV void tb_index(const TrainBatchArgs& a) {
     const int e = (int)(blockIdx.x * TB_T + threadIdx.x);
     if (e == 0) *a.step += 1;
     if (e >= a.n_eps) return;
@@ -45,7 +85,7 @@ BGX_DEV void tb_index(const TrainBatchArgs& a, int32_t* srcidx) {
     const int T = hi - lo;
     for (int s = lo; s < hi; ++s) {
         a.info[s] = T | (s == hi - 1 ? (int)0x80000000u : 0);
-        if constexpr (AFTER) srcidx[s] = s == hi - 1 ? ~e : s + 1;
+        if constexpr (AFTER) a.srcidx[s] = s == hi - 1 ? ~e : s + 1;
     }
 }
 

@@ -48,12 +48,12 @@ template <class T> bool read_all(const char* path, Buf<T>& b) {
     return ok;
 }
 
-void index_kernel(bgx::TrainAfterBatchArgs a) { bgx::tb_index<true>(a, a.srcidx); }
+void index_kernel(bgx::TrainBatchArgs a) { bgx::tb_index<true>(a); }
 
 // workgroup g takes tiles g, g + G, ... as the forward and backward launches do:
 // the first tile's source indices are requested before the loop, the next
 // tile's once this tile's rows are in
-void load_kernel(bgx::TrainAfterBatchArgs a, uint32_t* rows) {
+void load_kernel(bgx::TrainBatchArgs a, uint32_t* rows) {
     __shared__ uint32_t RW[bgx::TB_TILE][8];
     __shared__ int32_t SRC[bgx::TB_TILE];
     bgx::tb_stage_src(a.srcidx, a.n_rec, (long long)blockIdx.x * bgx::TB_TILE, SRC);
@@ -86,7 +86,7 @@ int main(int argc, char** argv) {
     hipMemsetAsync(info.get(), 0, (size_t)n_rec * sizeof(int32_t), nullptr);
     hipMemsetAsync(srcidx.get(), 0, (size_t)n_rec * sizeof(int32_t), nullptr);
     memset(rows.get(), 0xEE, (size_t)n_tiles * bgx::TB_TILE * 8 * sizeof(uint32_t));
-    bgx::TrainAfterBatchArgs a{};
+    bgx::TrainBatchArgs a{};
     a.rec = rec.p.get();
     a.offs = offs.p.get();
     a.n_eps = n_eps;

@@ -13,8 +13,6 @@ with the bounds of test_gpu_train_lambda.py.
 
 The inputs (train_afterstate_cases.py) carry random indicator bits in the
 headers and in every record's word 6: a loader that trusted them would show."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -22,14 +20,13 @@ import torch
 import train_afterstate_cases as ac
 import train_batch_cases as tc
 import train_lambda_cases as lc
-from test_gpu_train_lambda import _PM, _adam64, _state
-from test_gpu_train_zero_sum import run_td
+from train_gpu_runner import AFTER, TD, _PM, _adam64, _state, device_args, run
+from train_zero_sum_cases import TDF_ZERO_SUM as ZS
 
 pytestmark = pytest.mark.gpu
 
 GAMMA, LR = lc.GAMMA, 1e-3
 F32_FACTOR = lc.F32_FACTOR
-ZS = 1          # BGX_TDF_ZERO_SUM
 E_ARG = -1      # BGX_E_ARG
 _CACHE = {}
 CASES = list(ac.EMU_LENS) + ["two_tiles_each", "trailing"]
@@ -52,47 +49,6 @@ def _inputs(case):
     return _CACHE[case]
 
 
-def _call_after(d, lam, flags, lr=LR, clip=1.0, gamma=GAMMA, hdr_ptr="hdr", work_bytes=None):
-    """bgx_td_afterstate_update_batched on the device tensors of d; the return code."""
-    from bgx._lib import lib, ptr, stream_handle
-    return lib().bgx_td_afterstate_update_batched(
-        ptr(d["rec"]), ptr(d[hdr_ptr]) if hdr_ptr else None, ptr(d["offs"]), d["n_eps"], d["n_rec"], ptr(d["p"]),
-        ptr(d["m"]), ptr(d["v"]), ptr(d["step"]), lr, gamma, lam, flags, clip, ptr(d["met"]), ptr(d["grad"]),
-        ptr(d["tgt"]), ptr(d["work"]), d["work"].numel() if work_bytes is None else work_bytes, stream_handle())
-
-
-def _device(flat, m, v, step, hdr, rec, offs):
-    from bgx._lib import check, lib
-    dev = torch.device("cuda")
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(dev)   # noqa: E731
-    n_rec = len(rec)
-    need = ctypes.c_uint64(0)
-    check(lib().bgx_td_afterstate_batch_workspace(n_rec, ctypes.byref(need)))
-    lam_need = ctypes.c_uint64(0)
-    check(lib().bgx_tdlambda_batch_workspace(n_rec, ctypes.byref(lam_need)))
-    assert need.value == lam_need.value + 4 * ((n_rec + 3) // 4 * 4)   # the source index behind the lambda layout
-    return {"rec": torch.from_numpy(np.ascontiguousarray(rec).view(np.int32)).to(dev),
-            "hdr": torch.from_numpy(np.ascontiguousarray(hdr).view(np.int32)).to(dev), "offs": t(offs, np.int32),
-            "n_eps": len(offs) - 1, "n_rec": n_rec, "p": t(flat, np.float32), "m": t(m, np.float32),
-            "v": t(v, np.float32), "step": torch.tensor([int(step)], dtype=torch.int32, device=dev),
-            "met": torch.zeros(5, dtype=torch.float64, device=dev),
-            "grad": torch.full((len(flat),), float("nan"), dtype=torch.float32, device=dev),
-            "tgt": torch.full((n_rec,), float("nan"), dtype=torch.float32, device=dev),
-            "work": torch.empty(need.value, dtype=torch.uint8, device=dev)}
-
-
-def run_after(flat, m, v, step, hdr, rec, offs, lam, flags, lr=LR):
-    """One bgx_td_afterstate_update_batched call from host arrays; everything it writes, as numpy."""
-    from bgx._lib import check
-    d = _device(flat, m, v, step, hdr, rec, offs)
-    check(_call_after(d, lam, flags, lr=lr), "bgx_td_afterstate_update_batched")
-    torch.cuda.synchronize()
-    y = d["work"][:4 * d["n_rec"]].view(torch.float32).cpu().numpy().copy()   # the workspace starts with V of every record
-    return {"p": d["p"].cpu().numpy(), "m": d["m"].cpu().numpy(), "v": d["v"].cpu().numpy(),
-            "step": int(d["step"].item()), "grad": d["grad"].cpu().numpy(), "metrics": d["met"].cpu().numpy(),
-            "Y": y, "target": d["tgt"].cpu().numpy()}
-
-
 @pytest.mark.parametrize("wname", list(tc.WEIGHTS))
 @pytest.mark.parametrize("flags", [0, ZS], ids=["plain", "zero_sum"])
 @pytest.mark.parametrize("lam", [0.0, 0.7, 1.0])
@@ -109,8 +65,8 @@ def test_bit_identical_to_the_existing_call_on_rewritten_records(case, lam, flag
     a = {"p": flat, "m": m0, "v": v0, "step": 7}
     b = dict(a)
     for call in range(2):
-        a = run_after(a["p"], a["m"], a["v"], a["step"], hdr, rec, offs, lam, flags)
-        b = run_td(b["p"], b["m"], b["v"], b["step"], rec2, offs, lam, flags)
+        a = run(AFTER, a["p"], a["m"], a["v"], a["step"], rec, offs, lam, flags, hdr=hdr)
+        b = run(TD, b["p"], b["m"], b["v"], b["step"], rec2, offs, lam, flags)
         for k in ALL:
             x, y = (a[k][:covered], b[k][:covered]) if k in ("Y", "target") else (a[k], b[k])
             assert np.isfinite(x).all(), (call, k)
@@ -125,13 +81,13 @@ def test_same_call_twice_is_bit_identical():
     flat = tc.flat_params(tc.WEIGHTS["seed0"])
     hdr, rec, offs, _ = _inputs("two_tiles_each")
     m0, v0 = _state(len(flat), 8)
-    a = run_after(flat, m0, v0, 3, hdr, rec, offs, 0.7, ZS)
-    b = run_after(flat, m0, v0, 3, hdr, rec, offs, 0.7, ZS)
+    a = run(AFTER, flat, m0, v0, 3, rec, offs, 0.7, ZS, hdr=hdr)
+    b = run(AFTER, flat, m0, v0, 3, rec, offs, 0.7, ZS, hdr=hdr)
     for k in ALL:
         np.testing.assert_array_equal(a[k], b[k], err_msg=k)
     assert a["step"] == b["step"] == 4 and not np.array_equal(a["p"], flat)
     # the rows are not the records' own: the existing call on the records as they are gives another V
-    plain = run_td(flat, m0, v0, 3, rec, offs, 0.7, ZS)
+    plain = run(TD, flat, m0, v0, 3, rec, offs, 0.7, ZS)
     assert not np.array_equal(plain["Y"], a["Y"]) and not np.array_equal(plain["p"], a["p"])
 
 
@@ -141,22 +97,28 @@ def test_argument_errors_leave_the_state_untouched():
     flat = tc.flat_params(tc.WEIGHTS["seed0"])
     hdr, rec, offs, _ = _inputs("ragged_tile")
     m0, v0 = _state(len(flat), 6)
-    d = _device(flat, m0, v0, 5, hdr, rec, offs)
-    bad = [dict(lam=0.7, flags=0, hdr_ptr=None), dict(lam=0.7, flags=2), dict(lam=0.7, flags=ZS | 2),
+    from bgx import ops
+    d = device_args(AFTER, flat, m0, v0, 5, rec, offs, hdr=hdr)
+    p, m, v, step = d["state"]
+
+    def call(**kw):   # the return code
+        return ops.td_batched_call(AFTER, **{**d, "lr": LR, "gamma": GAMMA, "clip": 1.0, **kw})
+
+    bad = [dict(lam=0.7, flags=0, headers=None), dict(lam=0.7, flags=2), dict(lam=0.7, flags=ZS | 2),
            dict(lam=-0.01, flags=0), dict(lam=1.01, flags=ZS), dict(lam=float("nan"), flags=0),
            dict(lam=0.7, flags=ZS, work_bytes=d["work"].numel() - 1)]
     for kw in bad:
-        assert _call_after(d, **kw) == E_ARG, kw
+        assert call(**kw) == E_ARG, kw
     torch.cuda.synchronize()
-    np.testing.assert_array_equal(d["p"].cpu().numpy(), flat)
-    np.testing.assert_array_equal(d["m"].cpu().numpy(), m0)
-    np.testing.assert_array_equal(d["v"].cpu().numpy(), v0)
-    assert int(d["step"].item()) == 5 and not d["met"].cpu().numpy().any()
-    assert np.isnan(d["grad"].cpu().numpy()).all() and np.isnan(d["tgt"].cpu().numpy()).all()
+    np.testing.assert_array_equal(p.cpu().numpy(), flat)
+    np.testing.assert_array_equal(m.cpu().numpy(), m0)
+    np.testing.assert_array_equal(v.cpu().numpy(), v0)
+    assert int(step.item()) == 5 and not d["metrics"].cpu().numpy().any()
+    assert np.isnan(d["grad_out"].cpu().numpy()).all() and np.isnan(d["target_out"].cpu().numpy()).all()
     # the same tensors with valid arguments are accepted
-    assert _call_after(d, lam=0.7, flags=ZS) == 0
+    assert call(lam=0.7, flags=ZS) == 0
     torch.cuda.synchronize()
-    assert int(d["step"].item()) == 6
+    assert int(step.item()) == 6
 
 
 @pytest.mark.parametrize("wname", list(tc.WEIGHTS))
@@ -188,8 +150,8 @@ def test_afterstate_values_are_the_engines_own(wname):
     assert len(hdr) >= 20 and offs[-1] == len(rec) and (lens >= 1).all()
     flat = tc.flat_params(tc.WEIGHTS[wname])
     z = np.zeros_like(flat)
-    after = run_after(flat, z, z, 0, hdr, rec, offs, 0.7, ZS, lr=0.0)
-    before = run_td(flat, z, z, 0, rec, offs, 0.7, ZS, lr=0.0)
+    after = run(AFTER, flat, z, z, 0, rec, offs, 0.7, ZS, lr=0.0, hdr=hdr)
+    before = run(TD, flat, z, z, 0, rec, offs, 0.7, ZS, lr=0.0)
     f = rec[:, 7:9].copy().view(np.float32)
     err_a, err_s = np.abs(after["Y"] - f[:, 1]), np.abs(before["Y"] - f[:, 0])
     mv = ac.movers_of(rec)

@@ -2,21 +2,14 @@
 and V against the float64 restatement, its Adam stage against the fp32 one
 (bgx/train_ref.py), DeviceTrainer(batched=True, backend="hip") against the
 torch backend, reproducibility, and the sequential kernel left as it was.
-Inputs are synthetic harvests built on the host (train_batch_cases.py).
-
-The shapes are the smallest that reach each way the kernels can go wrong, in
-units of TILE (the backward launch's records per tile) and G (its largest
-grid): one record; a bootstrap across a tile edge and an episode edge at the
-same place; a ragged last tile with fewer tiles than workgroups; 2 G TILE + 7
-records (every workgroup sums over two tiles or more, the last one ragged); an
-episode of 2,100 records (longer than the sequential kernel's 2,048)."""
-import ctypes
-
+Inputs are synthetic harvests built on the host (train_batch_cases.py), in the
+shapes of train_gpu_runner.py (all but its last, which is the target stage's)."""
 import numpy as np
 import pytest
 import torch
 
 import train_batch_cases as tc
+from train_gpu_runner import CASES as SHAPES, TD0, _PM, _adam64, _inputs, run
 
 pytestmark = pytest.mark.gpu
 
@@ -24,29 +17,7 @@ GAMMA, LR = 0.99, 1e-3
 F32_FACTOR = 4.0   # what DESIGN section 4 "Numerics" grants an fp32 chain in another summation order
 Y_FLOOR_ULPS = 2    # fp32 ulps of max|Y64|: torch's own error can be 0 by chance (one record), a rounded fp32 V's cannot
 _CACHE = {}
-
-
-def _shape():
-    if "shape" not in _CACHE:
-        from bgx.trainer import DeviceTrainer
-        _CACHE["shape"] = DeviceTrainer.batch_shape()
-    return _CACHE["shape"]
-
-
-def _lens(case):
-    tile, grid = _shape()
-    return {"one": [1], "tile_edge_boot": [tile + 1], "tile_edge_episode_edge": [tile, 1],
-            "ragged_tile": [1, tile - 1, 2, 1, 3], "two_tiles_each": tc.ragged_lens(2 * grid * tile + 7, 11),
-            "long_episode": [2100]}[case]
-
-
-CASES = ("one", "tile_edge_boot", "tile_edge_episode_edge", "ragged_tile", "two_tiles_each", "long_episode")
-
-
-def _inputs(case):
-    if ("in", case) not in _CACHE:
-        _CACHE["in", case] = tc.synth(_lens(case), seed=100 + CASES.index(case))
-    return _CACHE["in", case]
+CASES = SHAPES[:6]
 
 
 def _ref64(case, wname):
@@ -57,37 +28,13 @@ def _ref64(case, wname):
     return _CACHE["r64", case, wname]
 
 
-def run_batched(flat, m, v, step, rec, offs, lr=LR, clip=1.0, gamma=GAMMA):
-    """One bgx_td0_update_batched call from host arrays; everything it writes, as numpy."""
-    from bgx._lib import check, lib, ptr, stream_handle
-    dev = torch.device("cuda")
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(dev)   # noqa: E731
-    d_rec = torch.from_numpy(np.ascontiguousarray(rec).view(np.int32)).to(dev)
-    d_offs = t(offs, np.int32)
-    d_p, d_m, d_v = t(flat, np.float32), t(m, np.float32), t(v, np.float32)
-    d_step = torch.tensor([int(step)], dtype=torch.int32, device=dev)
-    d_met = torch.zeros(5, dtype=torch.float64, device=dev)
-    d_grad = torch.full((d_p.numel(),), float("nan"), dtype=torch.float32, device=dev)
-    need = ctypes.c_uint64(0)
-    n_rec, n_eps = int(d_rec.shape[0]), len(offs) - 1
-    check(lib().bgx_td0_batch_workspace(n_rec, ctypes.byref(need)))
-    work = torch.empty(need.value, dtype=torch.uint8, device=dev)
-    check(lib().bgx_td0_update_batched(ptr(d_rec), ptr(d_offs), n_eps, n_rec, ptr(d_p), ptr(d_m), ptr(d_v),
-                                       ptr(d_step), lr, gamma, clip, ptr(d_met), ptr(d_grad), ptr(work),
-                                       need.value, stream_handle()), "bgx_td0_update_batched")
-    torch.cuda.synchronize()
-    y = work[:4 * n_rec].view(torch.float32).cpu().numpy().copy()   # the workspace starts with V of every record
-    return {"p": d_p.cpu().numpy(), "m": d_m.cpu().numpy(), "v": d_v.cpu().numpy(), "step": int(d_step.item()),
-            "grad": d_grad.cpu().numpy(), "metrics": d_met.cpu().numpy(), "Y": y}
-
-
 def _hip_lr0(case, wname):
     """The kernel's gradient of a case: lr = 0, zero moments (cached)."""
     if ("hip", case, wname) not in _CACHE:
         flat = tc.flat_params(tc.WEIGHTS[wname])
         _, rec, offs = _inputs(case)
         z = np.zeros_like(flat)
-        _CACHE["hip", case, wname] = run_batched(flat, z, z, 0, rec, offs, lr=0.0)
+        _CACHE["hip", case, wname] = run(TD0, flat, z, z, 0, rec, offs, lr=0.0)
     return _CACHE["hip", case, wname]
 
 
@@ -158,47 +105,20 @@ def test_adam_stage_against_fp32_restatement():
     flat = tc.flat_params(tc.WEIGHTS["ckpt"])
     _, rec, offs = _inputs("ragged_tile")
     z = np.zeros_like(flat)
-    a1 = run_batched(flat, z, z, 0, rec, offs, clip=1.0)
+    a1 = run(TD0, flat, z, z, 0, rec, offs, clip=1.0)
     r1 = _check_adam("clip 1.0", (flat, z, z, 0), a1, 1.0)
     assert float(r1["scale"]) < 1.0                # the clip was active
     assert a1["metrics"][1] == pytest.approx((len(offs) - 1) * float(r1["norm"] * r1["scale"]), rel=1e-6)
-    a0 = run_batched(flat, z, z, 0, rec, offs, clip=0.0)
+    a0 = run(TD0, flat, z, z, 0, rec, offs, clip=0.0)
     r0 = _check_adam("clip off", (flat, z, z, 0), a0, 0.0)
     assert float(r0["scale"]) == 1.0
-    a2 = run_batched(a1["p"], a1["m"], a1["v"], a1["step"], rec, offs, clip=1.0)
+    a2 = run(TD0, a1["p"], a1["m"], a1["v"], a1["step"], rec, offs, clip=1.0)
     _check_adam("second call", (a1["p"], a1["m"], a1["v"], 1), a2, 1.0)
     rng = np.random.default_rng(4)
     m0 = (rng.standard_normal(len(flat)) * 1e-3).astype(np.float32)
     v0 = (rng.random(len(flat)) * 1e-5).astype(np.float32)
-    a3 = run_batched(flat, m0, v0, 7, rec, offs, clip=1.0)
+    a3 = run(TD0, flat, m0, v0, 7, rec, offs, clip=1.0)
     _check_adam("non-zero state", (flat, m0, v0, 7), a3, 1.0)
-
-
-class _PM:
-    def __init__(self, sd):
-        self.sd = {k: v.clone() for k, v in sd.items()}
-
-    def get_parameters(self, device=None):
-        return {k: v.to(device) if device else v for k, v in self.sd.items()}
-
-    def set_parameters(self, sd):
-        self.sd = {k: v.detach().cpu().clone() for k, v in sd.items()}
-
-    def flat(self):
-        return np.concatenate([self.sd[k].numpy().reshape(-1) for k in ("fc1.weight", "fc1.bias",
-                                                                        "value_head.weight", "value_head.bias")])
-
-
-def _adam64(p, m, v, step, g, lr, clip):
-    """clip_grad_norm_ and Adam in float64."""
-    norm = np.sqrt((g * g).sum())
-    if clip > 0:
-        g = g * min(1.0, clip / (norm + 1e-6))
-    step += 1
-    m = m + (1.0 - 0.9) * (g - m)
-    v = v * 0.999 + (1.0 - 0.999) * g * g
-    den = np.sqrt(v) / np.sqrt(1.0 - 0.999 ** step) + 1e-8
-    return p - (lr / (1.0 - 0.9 ** step)) * m / den, m, v, step
 
 
 def test_trainer_hip_against_torch_backend_and_backend_swaps():
@@ -251,8 +171,8 @@ def test_same_call_twice_is_bit_identical():
     rng = np.random.default_rng(8)
     m0 = (rng.standard_normal(len(flat)) * 1e-3).astype(np.float32)
     v0 = (rng.random(len(flat)) * 1e-5).astype(np.float32)
-    a = run_batched(flat, m0, v0, 3, rec, offs)
-    b = run_batched(flat, m0, v0, 3, rec, offs)
+    a = run(TD0, flat, m0, v0, 3, rec, offs)
+    b = run(TD0, flat, m0, v0, 3, rec, offs)
     for k in ("p", "m", "v", "grad", "metrics", "Y"):
         assert np.array_equal(a[k], b[k]), k
     assert a["step"] == b["step"] == 4 and not np.array_equal(a["p"], flat)

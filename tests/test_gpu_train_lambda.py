@@ -5,45 +5,23 @@ bit-identical to bgx_td0_update_batched, lambda = 1 independent of the weights,
 reproducibility, DeviceTrainer(batched=True, backend="hip", lam=0.7) against
 the torch backend, and the TD(0) entry points left as they were.
 
-The shapes are test_gpu_train_batch.py's (one record; a bootstrap across a tile
+The shapes are train_gpu_runner.py's (one record; a bootstrap across a tile
 edge; an episode edge on a tile edge; a ragged tile; 2 G TILE + 7 records; an
-episode of 2,100 records), rebuilt here from DeviceTrainer.batch_shape(), and
-one harvest whose episode lengths put every width of the target stage's
-64-record chunks up to 256 at length - 1, equal and + 1."""
-import ctypes
-
+episode of 2,100 records; and one harvest whose episode lengths put every width
+of the target stage's 64-record chunks up to 256 at length - 1, equal and + 1)."""
 import numpy as np
 import pytest
 import torch
 
 import train_batch_cases as tc
 import train_lambda_cases as lc
-from test_gpu_train_batch import run_batched
+from train_gpu_runner import CASES, LAMBDA, TD0, _PM, _adam64, _inputs, _state, run
 
 pytestmark = pytest.mark.gpu
 
 GAMMA, LR = lc.GAMMA, 1e-3
 F32_FACTOR = lc.F32_FACTOR
 _CACHE = {}
-CASES = ("one", "tile_edge_boot", "tile_edge_episode_edge", "ragged_tile", "two_tiles_each", "long_episode", "edges")
-
-
-def _lens(case):
-    if "shape" not in _CACHE:
-        from bgx.trainer import DeviceTrainer
-        _CACHE["shape"] = DeviceTrainer.batch_shape()
-    tile, grid = _CACHE["shape"]
-    return {"one": [1], "tile_edge_boot": [tile + 1], "tile_edge_episode_edge": [tile, 1],
-            "ragged_tile": [1, tile - 1, 2, 1, 3], "two_tiles_each": tc.ragged_lens(2 * grid * tile + 7, 11),
-            "long_episode": [2100], "edges": lc.EDGE_LENS}[case]
-
-
-def _inputs(case):
-    if ("in", case) not in _CACHE:
-        _CACHE["in", case] = tc.synth(_lens(case), seed=100 + CASES.index(case))
-    return _CACHE["in", case]
-
-
 def _ref64(case, wname, lam):
     if ("r64", case, wname, lam) not in _CACHE:
         from bgx.train_ref import batched_td0_reference
@@ -53,40 +31,13 @@ def _ref64(case, wname, lam):
     return _CACHE["r64", case, wname, lam]
 
 
-def run_lambda(flat, m, v, step, rec, offs, lam, lr=LR, clip=1.0, gamma=GAMMA, want_target=True):
-    """One bgx_tdlambda_update_batched call from host arrays; everything it writes, as numpy."""
-    from bgx._lib import check, lib, ptr, stream_handle
-    dev = torch.device("cuda")
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(dev)   # noqa: E731
-    d_rec = torch.from_numpy(np.ascontiguousarray(rec).view(np.int32)).to(dev)
-    d_offs = t(offs, np.int32)
-    d_p, d_m, d_v = t(flat, np.float32), t(m, np.float32), t(v, np.float32)
-    d_step = torch.tensor([int(step)], dtype=torch.int32, device=dev)
-    d_met = torch.zeros(5, dtype=torch.float64, device=dev)
-    d_grad = torch.full((d_p.numel(),), float("nan"), dtype=torch.float32, device=dev)
-    need = ctypes.c_uint64(0)
-    n_rec, n_eps = int(d_rec.shape[0]), len(offs) - 1
-    d_tgt = torch.full((n_rec,), float("nan"), dtype=torch.float32, device=dev) if want_target else None
-    check(lib().bgx_tdlambda_batch_workspace(n_rec, ctypes.byref(need)))
-    work = torch.empty(need.value, dtype=torch.uint8, device=dev)
-    check(lib().bgx_tdlambda_update_batched(ptr(d_rec), ptr(d_offs), n_eps, n_rec, ptr(d_p), ptr(d_m), ptr(d_v),
-                                            ptr(d_step), lr, gamma, lam, clip, ptr(d_met), ptr(d_grad),
-                                            ptr(d_tgt) if want_target else None, ptr(work), need.value,
-                                            stream_handle()), "bgx_tdlambda_update_batched")
-    torch.cuda.synchronize()
-    y = work[:4 * n_rec].view(torch.float32).cpu().numpy().copy()   # the workspace starts with V of every record
-    return {"p": d_p.cpu().numpy(), "m": d_m.cpu().numpy(), "v": d_v.cpu().numpy(), "step": int(d_step.item()),
-            "grad": d_grad.cpu().numpy(), "metrics": d_met.cpu().numpy(), "Y": y,
-            "target": d_tgt.cpu().numpy() if want_target else None}
-
-
 def _hip_lr0(case, wname, lam):
     """The kernels' gradient and targets of a case: lr = 0, zero moments (cached)."""
     if ("hip", case, wname, lam) not in _CACHE:
         flat = tc.flat_params(tc.WEIGHTS[wname])
         _, rec, offs = _inputs(case)
         z = np.zeros_like(flat)
-        _CACHE["hip", case, wname, lam] = run_lambda(flat, z, z, 0, rec, offs, lam, lr=0.0)
+        _CACHE["hip", case, wname, lam] = run(LAMBDA, flat, z, z, 0, rec, offs, lam, lr=0.0)
     return _CACHE["hip", case, wname, lam]
 
 
@@ -126,11 +77,6 @@ def test_targets_value_and_gradient_against_float64(case, lam, wname):
         assert met[k] == pytest.approx(want[k], rel=1e-4, abs=1e-5), k
 
 
-def _state(n, seed):
-    rng = np.random.default_rng(seed)
-    return (rng.standard_normal(n) * 1e-3).astype(np.float32), (rng.random(n) * 1e-5).astype(np.float32)
-
-
 @pytest.mark.parametrize("case", ["ragged_tile", "two_tiles_each"])
 def test_lambda_zero_is_bit_identical_to_the_td0_call(case):
     """lambda = 0 through the new entry point, lr = 1e-3 and non-zero moments:
@@ -140,9 +86,9 @@ def test_lambda_zero_is_bit_identical_to_the_td0_call(case):
     flat = tc.flat_params(tc.WEIGHTS["ckpt"])
     _, rec, offs = _inputs(case)
     m0, v0 = _state(len(flat), 4)
-    a = run_batched(flat, m0, v0, 7, rec, offs)
+    a = run(TD0, flat, m0, v0, 7, rec, offs)
     for want_target in (True, False):
-        b = run_lambda(flat, m0, v0, 7, rec, offs, 0.0, want_target=want_target)
+        b = run(LAMBDA, flat, m0, v0, 7, rec, offs, 0.0, want_target=want_target)
         for k in ("p", "m", "v", "grad", "metrics", "Y"):
             assert np.array_equal(a[k], b[k]), (k, want_target)
         assert a["step"] == b["step"] == 8 and not np.array_equal(a["p"], flat)
@@ -171,38 +117,11 @@ def test_same_call_twice_is_bit_identical():
     flat = tc.flat_params(tc.WEIGHTS["seed0"])
     _, rec, offs = _inputs("two_tiles_each")
     m0, v0 = _state(len(flat), 8)
-    a = run_lambda(flat, m0, v0, 3, rec, offs, 0.7)
-    b = run_lambda(flat, m0, v0, 3, rec, offs, 0.7)
+    a = run(LAMBDA, flat, m0, v0, 3, rec, offs, 0.7)
+    b = run(LAMBDA, flat, m0, v0, 3, rec, offs, 0.7)
     for k in ("p", "m", "v", "grad", "metrics", "Y", "target"):
         assert np.array_equal(a[k], b[k]), k
     assert a["step"] == b["step"] == 4 and not np.array_equal(a["p"], flat)
-
-
-class _PM:
-    def __init__(self, sd):
-        self.sd = {k: v.clone() for k, v in sd.items()}
-
-    def get_parameters(self, device=None):
-        return {k: v.to(device) if device else v for k, v in self.sd.items()}
-
-    def set_parameters(self, sd):
-        self.sd = {k: v.detach().cpu().clone() for k, v in sd.items()}
-
-    def flat(self):
-        return np.concatenate([self.sd[k].numpy().reshape(-1) for k in ("fc1.weight", "fc1.bias",
-                                                                        "value_head.weight", "value_head.bias")])
-
-
-def _adam64(p, m, v, step, g, lr, clip):
-    """clip_grad_norm_ and Adam in float64."""
-    norm = np.sqrt((g * g).sum())
-    if clip > 0:
-        g = g * min(1.0, clip / (norm + 1e-6))
-    step += 1
-    m = m + (1.0 - 0.9) * (g - m)
-    v = v * 0.999 + (1.0 - 0.999) * g * g
-    den = np.sqrt(v) / np.sqrt(1.0 - 0.999 ** step) + 1e-8
-    return p - (lr / (1.0 - 0.9 ** step)) * m / den, m, v, step
 
 
 def test_trainer_hip_against_torch_backend_and_backend_swaps():
@@ -265,14 +184,14 @@ def test_td0_entry_points_are_unchanged_by_a_lambda_call():
     hdr, srec, _ = tc.synth(tc.ragged_lens(1500, 21, 1, 90), seed=22)
     batched, seq = [], []
     for k in range(2):
-        batched.append(run_batched(flat, m0, v0, 2, rec, offs))
+        batched.append(run(TD0, flat, m0, v0, 2, rec, offs))
         pm = _PM(sd0)
         t = DeviceTrainer(pm, device="cuda", batch_episode_size=len(hdr))
         assert t.backend == "hip" and not t.batched and t.lam == 0.0
         met = t.update_records(hdr, srec)
         seq.append((pm.flat(), met))
         if k == 0:
-            lam_out = run_lambda(flat, m0, v0, 2, rec, offs, 0.7)
+            lam_out = run(LAMBDA, flat, m0, v0, 2, rec, offs, 0.7)
             assert not np.array_equal(lam_out["p"], batched[0]["p"])
             pb = _PM(sd0)
             DeviceTrainer(pb, device="cuda", batched=True, backend="hip", lam=0.7).update_records(hdr, srec)

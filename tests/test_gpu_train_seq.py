@@ -17,6 +17,7 @@ import torch
 
 import train_batch_cases as tc
 import train_seq_cases as sc
+from train_gpu_runner import _PM
 
 pytestmark = pytest.mark.gpu
 
@@ -189,21 +190,6 @@ def test_adam_step_from_a_non_zero_state(case, wname, step0):
     v0 = (rng.random(len(flat)) * 1e-5).astype(np.float32)
     _, r = _check_adam(f"step {step0}", case, wname, m0, v0, step0, 1.0)
     assert (float(r["scale"]) < 1.0) == (case in sc.CLIP_ACTIVE[wname])
-
-
-class _PM:
-    def __init__(self, sd):
-        self.sd = {k: v.clone() for k, v in sd.items()}
-
-    def get_parameters(self, device=None):
-        return {k: v.to(device) if device else v for k, v in self.sd.items()}
-
-    def set_parameters(self, sd):
-        self.sd = {k: v.detach().cpu().clone() for k, v in sd.items()}
-
-    def flat(self):
-        return np.concatenate([self.sd[k].numpy().reshape(-1) for k in ("fc1.weight", "fc1.bias",
-                                                                        "value_head.weight", "value_head.bias")])
 
 
 @pytest.mark.parametrize("wname", list(tc.WEIGHTS))

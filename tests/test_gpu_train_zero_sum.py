@@ -7,13 +7,11 @@ flag set, the flag reaching the update, reproducibility,
 DeviceTrainer(batched=True, backend="hip", zero_sum=True) against the torch
 backend, and the existing entry points left as they were.
 
-The shapes are test_gpu_train_lambda.py's. The records carry the movers they
+The shapes are train_gpu_runner.py's. The records carry the movers they
 were drawn with (about every second pair of neighbours changes the mover); two
 more cases rewrite them (word 11 bit 9 and word 6 bit 16): alternating, and a
 single change 64 records before each episode's end, the edge between the target
 stage's last two chunks."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -21,8 +19,7 @@ import torch
 import train_batch_cases as tc
 import train_lambda_cases as lc
 import train_zero_sum_cases as zc
-from test_gpu_train_batch import run_batched
-from test_gpu_train_lambda import CASES as SHAPES, _PM, _adam64, _inputs as _shape_inputs, _state, run_lambda
+from train_gpu_runner import CASES as SHAPES, LAMBDA, TD, TD0, _PM, _adam64, _inputs as _shape_inputs, _state, run
 
 pytestmark = pytest.mark.gpu
 
@@ -38,33 +35,6 @@ def _inputs(shape, pattern="drawn"):
         hdr, rec, offs = _shape_inputs(shape)
         _CACHE["in", shape, pattern] = (hdr, zc.with_pattern(rec, offs, pattern), offs)
     return _CACHE["in", shape, pattern]
-
-
-def run_td(flat, m, v, step, rec, offs, lam, flags, lr=LR, clip=1.0, gamma=GAMMA, want_target=True):
-    """One bgx_td_update_batched call from host arrays; everything it writes, as numpy."""
-    from bgx._lib import check, lib, ptr, stream_handle
-    dev = torch.device("cuda")
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(dev)   # noqa: E731
-    d_rec = torch.from_numpy(np.ascontiguousarray(rec).view(np.int32)).to(dev)
-    d_offs = t(offs, np.int32)
-    d_p, d_m, d_v = t(flat, np.float32), t(m, np.float32), t(v, np.float32)
-    d_step = torch.tensor([int(step)], dtype=torch.int32, device=dev)
-    d_met = torch.zeros(5, dtype=torch.float64, device=dev)
-    d_grad = torch.full((d_p.numel(),), float("nan"), dtype=torch.float32, device=dev)
-    need = ctypes.c_uint64(0)
-    n_rec, n_eps = int(d_rec.shape[0]), len(offs) - 1
-    d_tgt = torch.full((n_rec,), float("nan"), dtype=torch.float32, device=dev) if want_target else None
-    check(lib().bgx_tdlambda_batch_workspace(n_rec, ctypes.byref(need)))
-    work = torch.empty(need.value, dtype=torch.uint8, device=dev)
-    check(lib().bgx_td_update_batched(ptr(d_rec), ptr(d_offs), n_eps, n_rec, ptr(d_p), ptr(d_m), ptr(d_v),
-                                      ptr(d_step), lr, gamma, lam, flags, clip, ptr(d_met), ptr(d_grad),
-                                      ptr(d_tgt) if want_target else None, ptr(work), need.value,
-                                      stream_handle()), "bgx_td_update_batched")
-    torch.cuda.synchronize()
-    y = work[:4 * n_rec].view(torch.float32).cpu().numpy().copy()   # the workspace starts with V of every record
-    return {"p": d_p.cpu().numpy(), "m": d_m.cpu().numpy(), "v": d_v.cpu().numpy(), "step": int(d_step.item()),
-            "grad": d_grad.cpu().numpy(), "metrics": d_met.cpu().numpy(), "Y": y,
-            "target": d_tgt.cpu().numpy() if want_target else None}
 
 
 ALL = ("p", "m", "v", "grad", "metrics", "Y", "target")
@@ -92,7 +62,7 @@ def test_targets_value_and_gradient_against_float64(case, lam, wname):
     _, rec, offs = _inputs(shape, pattern)
     r64 = batched_td0_reference(flat, rec, offs, GAMMA, lam=lam, zero_sum=True)
     z = np.zeros_like(flat)
-    hip = run_td(flat, z, z, 0, rec, offs, lam, ZS, lr=0.0)
+    hip = run(TD, flat, z, z, 0, rec, offs, lam, ZS, lr=0.0)
     g32, loss32, y32, t32 = zc.torch_zero_sum_grad(flat, rec, offs, GAMMA, lam, torch.float32, device="cuda")
     err_hip, err_t32 = lc.rel_err(hip["grad"], r64["grad"]), lc.rel_err(g32, r64["grad"])
     ey_hip, ey_t32 = lc.rel_err(hip["Y"], r64["Y"]), lc.rel_err(y32, r64["Y"])
@@ -125,8 +95,8 @@ def test_flags_zero_is_bit_identical_to_the_lambda_call(shape, lam):
     mv = zc.movers_of(rec)
     assert (mv[1:] != mv[:-1]).any()
     m0, v0 = _state(len(flat), 4)
-    a = run_lambda(flat, m0, v0, 7, rec, offs, lam)
-    b = run_td(flat, m0, v0, 7, rec, offs, lam, 0)
+    a = run(LAMBDA, flat, m0, v0, 7, rec, offs, lam)
+    b = run(TD, flat, m0, v0, 7, rec, offs, lam, 0)
     for k in ALL:
         assert np.array_equal(a[k], b[k]), k
     assert a["step"] == b["step"] == 8 and not np.array_equal(a["p"], flat)
@@ -143,8 +113,8 @@ def test_one_mover_everywhere_is_the_lambda_call(lam):
     for shape in ("edges", "two_tiles_each"):
         _, rec, offs = _inputs(shape, "equal")
         assert not zc.movers_of(rec).any()
-        a = run_lambda(flat, m0, v0, 7, rec, offs, lam)
-        b = run_td(flat, m0, v0, 7, rec, offs, lam, ZS)
+        a = run(LAMBDA, flat, m0, v0, 7, rec, offs, lam)
+        b = run(TD, flat, m0, v0, 7, rec, offs, lam, ZS)
         for k in (ALL if lam != 0.0 else ("Y", "target")):
             assert np.array_equal(a[k], b[k]), (shape, k)
         assert a["step"] == b["step"] == 8
@@ -155,9 +125,9 @@ def test_alternating_movers_reach_the_update_and_the_call_is_reproducible():
     m0, v0 = _state(len(flat), 8)
     for lam in (0.0, 0.7):
         _, rec, offs = _inputs("two_tiles_each", "alternating")
-        plain = run_lambda(flat, m0, v0, 3, rec, offs, lam)
-        a = run_td(flat, m0, v0, 3, rec, offs, lam, ZS)
-        b = run_td(flat, m0, v0, 3, rec, offs, lam, ZS)
+        plain = run(LAMBDA, flat, m0, v0, 3, rec, offs, lam)
+        a = run(TD, flat, m0, v0, 3, rec, offs, lam, ZS)
+        b = run(TD, flat, m0, v0, 3, rec, offs, lam, ZS)
         for k in ALL:
             assert np.array_equal(a[k], b[k]), (lam, k)
         assert a["step"] == b["step"] == 4 and not np.array_equal(a["p"], flat)
@@ -226,15 +196,15 @@ def test_existing_entry_points_are_unchanged_by_a_zero_sum_call():
     hdr, srec, _ = tc.synth(tc.ragged_lens(1500, 21, 1, 90), seed=22)
     batched, lam, seq = [], [], []
     for k in range(2):
-        batched.append(run_batched(flat, m0, v0, 2, rec, offs))
-        lam.append(run_lambda(flat, m0, v0, 2, rec, offs, 0.7))
+        batched.append(run(TD0, flat, m0, v0, 2, rec, offs))
+        lam.append(run(LAMBDA, flat, m0, v0, 2, rec, offs, 0.7))
         pm = _PM(sd0)
         t = DeviceTrainer(pm, device="cuda", batch_episode_size=len(hdr))
         assert t.backend == "hip" and not t.batched and t.lam == 0.0 and not t.zero_sum
         met = t.update_records(hdr, srec)
         seq.append((pm.flat(), met))
         if k == 0:
-            zs = run_td(flat, m0, v0, 2, rec, offs, 0.7, ZS)
+            zs = run(TD, flat, m0, v0, 2, rec, offs, 0.7, ZS)
             assert not np.array_equal(zs["p"], lam[0]["p"])
             pb = _PM(sd0)
             DeviceTrainer(pb, device="cuda", batched=True, backend="hip", lam=0.7, zero_sum=True).update_records(hdr, srec)

@@ -6,8 +6,8 @@ import numpy as np
 
 import train_batch_cases as tc
 import train_lambda_cases as lc
+from bgx.ops import TDF_ZERO_SUM  # noqa: F401  (BGX_TDF_ZERO_SUM, for the tests that pass flags)
 
-TDF_ZERO_SUM = 1   # BGX_TDF_ZERO_SUM (include/bgx.h)
 # a single mover change this many records before an episode's end: the edge between the target
 # stage's last two 64-record chunks (the flip of lane 63) and its two neighbours
 FLIP_AT = (63, 64, 65)

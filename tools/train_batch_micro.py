@@ -21,7 +21,6 @@ episodes/s and records/s of each and the batched call's TFLOP/s, counting
 the 157.3 TF f32-MFMA peak. --only hip runs the batched call alone (for a
 kernel trace, which gives the launches' shares)."""
 import argparse
-import ctypes
 import json
 import os
 import statistics
@@ -36,6 +35,7 @@ sys.path[:0] = [os.path.join(REPO, "mlp-ppo-2ply-multi_amd"), os.path.join(REPO,
 from bgx import Engine  # noqa: E402
 from bgx._lib import check, lib, ptr, stream_handle  # noqa: E402
 from bgx.net import BackgammonPolicyNetwork  # noqa: E402
+from bgx import ops  # noqa: E402
 from bgx.ops import weights_from  # noqa: E402
 from bgx.trainer import DeviceTrainer  # noqa: E402
 from train_loop import LocalPM  # noqa: E402
@@ -102,7 +102,6 @@ def main():
     dev =torch.device("cuda")
     torch.manual_seed(0)
     pm, hdr_all, rec_all = harvest(max(args.sizes))
-    L = lib()
     out = []
     for n_eps in args.sizes:
         hdr = hdr_all[:n_eps]
@@ -111,77 +110,48 @@ def main():
         rec = rec_all[:n_rec].contiguous()
         offs = torch.as_tensor(np.concatenate([[0], np.cumsum(lens)]).astype(np.int32), device=dev)
         row = {"episodes": n_eps, "records": n_rec}
-        # ---- the batched HIP call
-        p, m, v, step = flat_state(pm, dev)
-        need = ctypes.c_uint64(0)
-        check(L.bgx_td0_batch_workspace(n_rec, ctypes.byref(need)))
-        work = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        # ---- the batched HIP entries, each timed by name on the same records from a fresh state
+        def batched_ms(entry, **kw):
+            p, m, v, step = flat_state(pm, dev)
+            work = torch.empty(ops.td_batched_workspace(entry, n_rec), dtype=torch.uint8, device=dev)
+            return event_ms(lambda: ops.td_batched(entry, records=rec, offs=offs, n_eps=n_eps, n_rec=n_rec,
+                                                   state=(p, m, v, step), lr=1e-3, gamma=0.99, clip=1.0, metrics=met,
+                                                   work=work, stream=stream, **kw), args.reps)
+
+        def rates(ms):
+            return {"ms": ms, "episodes_per_s": n_eps / ms * 1e3, "records_per_s": n_rec / ms * 1e3}
+
         met = torch.zeros(5, dtype=torch.float64, device=dev)
-        s = stream_handle()
-
-        def batched():
-            check(L.bgx_td0_update_batched(ptr(rec), ptr(offs), n_eps, n_rec, ptr(p), ptr(m), ptr(v), ptr(step),
-                                           1e-3, 0.99, 1.0, ptr(met), None, ptr(work), need.value, s))
-
-        ms = event_ms(batched, args.reps)
-        row["batched_hip"] = {"ms": ms, "episodes_per_s": n_eps / ms * 1e3, "records_per_s": n_rec / ms * 1e3,
-                              "tflops": n_rec * FLOP_PER_RECORD / ms * 1e-9,
+        stream = torch.cuda.current_stream()
+        ms = batched_ms("bgx_td0_update_batched")
+        row["batched_hip"] = {**rates(ms), "tflops": n_rec * FLOP_PER_RECORD / ms * 1e-9,
                               "of_f32_mfma_peak": n_rec * FLOP_PER_RECORD / ms * 1e-9 / PEAK_TF}
         if args.lam is not None:
-            # ---- the TD(lambda) call: the same launches and the target stage between forward and backward
-            p, m, v, step = flat_state(pm, dev)
-            need_l = ctypes.c_uint64(0)
-            check(L.bgx_tdlambda_batch_workspace(n_rec, ctypes.byref(need_l)))
-            work_l = torch.empty(need_l.value, dtype=torch.uint8, device=dev)
-
-            def batched_lambda():
-                check(L.bgx_tdlambda_update_batched(ptr(rec), ptr(offs), n_eps, n_rec, ptr(p), ptr(m), ptr(v),
-                                                    ptr(step), 1e-3, 0.99, args.lam, 1.0, ptr(met), None, None,
-                                                    ptr(work_l), need_l.value, s))
-
-            ms_l = event_ms(batched_lambda, args.reps)
-            row["lambda_hip"] = {"lam": args.lam, "ms": ms_l, "episodes_per_s": n_eps / ms_l * 1e3,
-                                 "records_per_s": n_rec / ms_l * 1e3, "over_td0": ms_l / ms}
-            if args.zero_sum:
-                # ---- the zero-sum call: the lambda call's launches with the target stage's zero-sum instance
-                p, m, v, step = flat_state(pm, dev)
-
-                def batched_zero_sum():
-                    check(L.bgx_td_update_batched(ptr(rec), ptr(offs), n_eps, n_rec, ptr(p), ptr(m), ptr(v),
-                                                  ptr(step), 1e-3, 0.99, args.lam, 1, 1.0, ptr(met), None, None,
-                                                  ptr(work_l), need_l.value, s))
-
-                ms_z = event_ms(batched_zero_sum, args.reps)
-                row["zero_sum_hip"] = {"lam": args.lam, "ms": ms_z, "episodes_per_s": n_eps / ms_z * 1e3,
-                                       "records_per_s": n_rec / ms_z * 1e3, "over_lambda": ms_z / ms_l,
-                                       "extra_us": (ms_z - ms_l) * 1e3}
-                if args.afterstates:
-                    # ---- the afterstate call: the zero-sum call's launches on afterstate rows
-                    p, m, v, step = flat_state(pm, dev)
-                    d_hdr = hdr.to(torch.int32).contiguous().to(dev)
-                    need_a = ctypes.c_uint64(0)
-                    check(L.bgx_td_afterstate_batch_workspace(n_rec, ctypes.byref(need_a)))
-                    work_a = torch.empty(need_a.value, dtype=torch.uint8, device=dev)
-
-                    def batched_afterstate():
-                        check(L.bgx_td_afterstate_update_batched(ptr(rec), ptr(d_hdr), ptr(offs), n_eps, n_rec, ptr(p),
-                                                                 ptr(m), ptr(v), ptr(step), 1e-3, 0.99, args.lam, 1, 1.0,
-                                                                 ptr(met), None, None, ptr(work_a), need_a.value, s))
-
-                    ms_a = event_ms(batched_afterstate, args.reps)
-                    row["afterstate_hip"] = {"lam": args.lam, "ms": ms_a, "episodes_per_s": n_eps / ms_a * 1e3,
-                                             "records_per_s": n_rec / ms_a * 1e3, "over_zero_sum": ms_a / ms_z,
-                                             "extra_us": (ms_a - ms_z) * 1e3}
+            # the same launches and the target stage between forward and backward
+            ms_l = batched_ms("bgx_tdlambda_update_batched", lam=args.lam)
+            row["lambda_hip"] = {"lam": args.lam, **rates(ms_l), "over_td0": ms_l / ms}
+        if args.zero_sum:
+            # the lambda call's launches with the target stage's zero-sum instance
+            ms_z = batched_ms("bgx_td_update_batched", lam=args.lam, flags=ops.TDF_ZERO_SUM)
+            row["zero_sum_hip"] = {"lam": args.lam, **rates(ms_z), "over_lambda": ms_z / ms_l,
+                                   "extra_us": (ms_z - ms_l) * 1e3}
+        if args.afterstates:
+            # the zero-sum call's launches on afterstate rows
+            ms_a = batched_ms("bgx_td_afterstate_update_batched", headers=hdr.to(torch.int32).contiguous().to(dev),
+                              lam=args.lam, flags=ops.TDF_ZERO_SUM)
+            row["afterstate_hip"] = {"lam": args.lam, **rates(ms_a), "over_zero_sum": ms_a / ms_z,
+                                     "extra_us": (ms_a - ms_z) * 1e3}
         if args.only is None:
             # ---- the sequential kernel (one Adam step per episode)
             p, m, v, step = flat_state(pm, dev)
+            s = stream_handle(stream)
 
             def sequential():
-                check(L.bgx_td0_update(ptr(rec), ptr(offs), n_eps, ptr(p), ptr(m), ptr(v), ptr(step), 1e-3, 0.99,
-                                       1.0, ptr(met), s))
+                check(lib().bgx_td0_update(ptr(rec), ptr(offs), n_eps, ptr(p), ptr(m), ptr(v), ptr(step), 1e-3, 0.99,
+                                           1.0, ptr(met), s))
 
             ms = event_ms(sequential, min(args.reps, 5))
-            row["sequential"] = {"ms": ms, "episodes_per_s": n_eps / ms * 1e3, "records_per_s": n_rec / ms * 1e3}
+            row["sequential"] = rates(ms)
             # ---- the eager torch batched path
             tr = DeviceTrainer(pm, device="cuda", batch_episode_size=n_eps, batched=True, backend="torch")
             reps = min(args.torch_max_reps, args.reps) if n_eps <= 2000 else 2
